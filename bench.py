@@ -6,9 +6,15 @@ Llama-3-8B, per-tensor FP8 linears, TP = --gpus, batch 128, KV length 2048, bf16
 One "step" = one decode step of the whole layer stack through the plugin surfaces
 (MiAttnBackend.init_forward_metadata + forward, Fp8LinearMethod.apply, plus the glue kernels and
 the bf16 lm_head), captured once in a hipGraph and replayed.  Inputs (weights, KV pool,
-req_to_token) are resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
+req_to_token) are resident in HBM before the timed region and identical from run to run (every
+random draw is seeded).  Prints ONE JSON line (rank 0).
 
-  python bench.py --gpus 1 --steps 20 --warmup 3
+A plain run sets up, warms up, times --steps steps and prints the headline.  --dump-outputs DIR
+also writes what the last timed step returned (DIR/*.npy).  --full adds every other measurement:
+per-step synchronised median, plugin-surface-only step, communication overlap (TP > 1), decode
+attention roofline, ragged decode attention, the prefill leg and the CPU baseline.
+
+  python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W          (TP=N over RCCL)
 """
@@ -41,7 +47,13 @@ def parse():
     ap.add_argument("--layers", type=int, default=0, help="override layer count (debug only; invalidates the metric)")
     ap.add_argument("--contiguous", action="store_true", help="contiguous KV slots instead of scattered")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary measurements: synchronised median, plugin-surface-only "
+                         "step, communication overlap, attention roofline, ragged attention, prefill leg, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy: next_token_ids, and a fixed seeded "
+                         "sample of the logit columns (logits_sample, logits_sample_columns)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--act-scheme", choices=["static", "dynamic"], default="static",
                     help="FP8 activation scale: static = serialized FP8 checkpoint with calibrated per-tensor "
                          "input scales (the reference's own FP8 test model format), dynamic = bf16 checkpoint "
@@ -51,19 +63,19 @@ def parse():
     ap.add_argument("--no-custom-ar", action="store_true", help="TP>1: use RCCL only (skip the native xGMI all-reduce)")
     ap.add_argument("--splits", type=int, default=0, help="force the split-KV count (0 = backend heuristic)")
     ap.add_argument("--prefill-batch", type=int, default=-1,
-                    help="sequences of --seq tokens in the prefill leg (-1 = the decode batch: the metric's 128 x 2048; 0 = skip)")
+                    help="sequences of --seq tokens in the prefill leg (with --full; -1 = the decode batch: the metric's 128 x 2048; 0 = skip)")
     ap.add_argument("--prefill-chunk", type=int, default=8,
                     help="sequences per EXTEND batch of the prefill leg (8 x 2048 tokens: the 134-MB activations between the "
                          "GEMMs and the norm / rope / KV-write kernels stay in the 256-MB Infinity Cache; measured on one box: "
                          "2 -> 1942, 4 -> 2021, 8 -> 2044, 16 -> 2015, 32 -> 2012 TFLOP/s)")
-    ap.add_argument("--no-plugin-surface", action="store_true", help="skip the unfused plugin-surface-only step timing")
+    ap.add_argument("--no-plugin-surface", action="store_true", help="with --full: skip the unfused plugin-surface-only step timing")
     ap.add_argument("--tbo", choices=["auto", "on", "off"], default="auto",
                     help="two-micro-batch overlap of the decode step (each half of the batch on its own stream, own "
                          "all-reduce communicator): auto = on for TP > 1 (C5: all-reduce overlapped with attention)")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="KV cache dtype: bf16 is BASELINE.json's configuration (the headline); fp8 = e4m3fn pool "
                          "(SURVEY 8f row 1), reported as a variant -- a different workload, not the headline")
-    ap.add_argument("--kernel-reps", type=int, default=3, help="passes over all layers for the roofline timing")
+    ap.add_argument("--kernel-reps", type=int, default=3, help="passes over all layers for the roofline timing (with --full)")
     return ap.parse_args()
 
 
@@ -296,6 +308,22 @@ def prefill_leg(H, stack, runner, backend, shape, nseq, S, dev, world, chunk=16)
                       f"flops = linears {lin:.3e} + causal attention {attn:.3e} + lm_head {head:.3e}"}
 
 
+DUMP_LOGIT_COLUMNS = 32768      # of the vocabulary's 128256: 128 rows x 32768 columns x 4 B = 16.8 MB
+
+
+def dump_outputs(path, logits, out_ids):
+    """What a caller of the timed step receives, from its last execution: the next token ids, and the logits they are
+    the argmax of -- every row, a fixed seeded sample of the columns (the whole array in float32 would pass 64 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    vocab = logits.shape[1]
+    cols = torch.randperm(vocab, generator=torch.Generator().manual_seed(0))[:DUMP_LOGIT_COLUMNS].sort().values
+    sample = logits.index_select(1, cols.to(logits.device)).float().cpu()
+    np.save(os.path.join(path, "next_token_ids.npy"), out_ids.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "logits_sample.npy"), sample.numpy())
+    np.save(os.path.join(path, "logits_sample_columns.npy"), cols.numpy().astype(np.float64))
+
+
 def cpu_baseline(shape, B, S, sample_requests=64, timed_layers=12):
     """The reference's torch-native arithmetic (our CPU restatement, oracle/) for ONE decoder layer,
     timed on the host cores on a bounded sample: linears / norm / rope / activation at the full batch
@@ -380,6 +408,7 @@ def main():
         faulthandler.dump_traceback_later(int(os.environ["MI_BENCH_WATCHDOG"]), exit=True)
     world, rank, local, group = dist_setup(a.gpus, a.dist_backend)
     dev = torch.device("cuda", local)
+    torch.manual_seed(0)                        # token ids and every other unnamed draw: the same from run to run
     from iaas_sglang_amd import harness as H
     from iaas_sglang_amd.attention_backend import MiAttnBackend
     from iaas_sglang_amd.quantization import Fp8Config
@@ -423,6 +452,7 @@ def main():
         backend.init_forward_metadata(fb)
         logits = stack.forward(hidden, fb.positions, fb, backend)
         torch.argmax(logits, dim=-1, out=out_ids)
+        return logits
 
     serial_step = step
     if tbo:
@@ -438,14 +468,15 @@ def main():
             hidden = torch.index_select(stack.embed, 0, ids)
             logits = stack.forward_decode_two_batch(hidden, fb.positions, halves, [backend, backend_b], tbo_streams, tbo_ars)
             torch.argmax(logits, dim=-1, out=out_ids)
+            return logits
 
     def capture(fn):
-        """hipGraph of one step (None when capture is impossible, e.g. gloo collectives): eager once on a side stream
-        (allocator warm-up, lazy inits), then the capture."""
+        """hipGraph of one step and the logits tensor every replay of it fills (None, None when capture is impossible,
+        e.g. gloo collectives): eager once on a side stream (allocator warm-up, lazy inits), then the capture."""
         fn()
         barrier_sync(world)
         if a.no_graph or not (world == 1 or a.dist_backend == "nccl"):
-            return None
+            return None, None
         try:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -458,22 +489,22 @@ def main():
                     if ca is not None:
                         es.enter_context(ca.capture())
                 with torch.cuda.graph(g):
-                    fn()
-            return g
+                    out = fn()
+            return g, out
         except Exception as e:  # e.g. a collective that cannot be captured: fall back to eager launches
             if rank == 0:
                 print(f"[bench] graph capture failed ({type(e).__name__}: {e}); running eager", file=sys.stderr)
             torch.cuda.synchronize()
-            return None
+            return None, None
 
-    graph = capture(step)
+    graph, logits = capture(step)
     run = graph.replay if graph is not None else step
     timed_is_tbo = tbo
     tbo_auto_note = None
     if tbo and a.tbo == "auto":
         # auto: the two-micro-batch step is the timed one only if it is the faster one on this machine -- a short synced
         # comparison (max over ranks, so every rank takes the same branch) before the timed region
-        g_ser = capture(serial_step)
+        g_ser, logits_ser = capture(serial_step)
         run_ser = g_ser.replay if g_ser is not None else serial_step
 
         def quick(fn, n=3):
@@ -489,20 +520,23 @@ def main():
         q_tbo, q_ser = quick(run), quick(run_ser)
         tbo_auto_note = f"auto: two-batch {q_tbo:.3f} ms vs serial {q_ser:.3f} ms in a 3-step comparison"
         if q_ser < q_tbo:
-            run, graph, timed_is_tbo = run_ser, g_ser, False
+            run, graph, logits, timed_is_tbo = run_ser, g_ser, logits_ser, False
 
     for _ in range(a.warmup):
         run()
+    last = None
     barrier_sync(world)
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        run()
+        last = run()                              # eager launches: the logits; a graph replay fills `logits`
     barrier_sync(world)
     elapsed = time.perf_counter() - t0
     from iaas_sglang_amd.parallel import max_over_ranks
     elapsed = max_over_ranks(elapsed, world, dev)
     ms_per_step = elapsed / a.steps * 1e3
     tokens_per_s = B / (ms_per_step * 1e-3)          # TP: one batch of B tokens per step for the whole job
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, logits if graph is not None else last, out_ids)
 
     def synced_median(fn, n):
         """bench_one_batch.latency_test_run_once (bench_one_batch.py:332-430): every decode step bracketed by a device
@@ -516,10 +550,11 @@ def main():
             lat.append(time.perf_counter() - t)
         return max_over_ranks(sorted(lat)[len(lat) // 2], world, dev) * 1e3
 
-    median_ms = synced_median(run, max(5, a.steps))
+    # ---- everything below the headline is measured with --full only
+    median_ms = synced_median(run, max(5, a.steps)) if a.full else None
 
     def time_variant(fn):
-        g_ = capture(fn)
+        g_, _ = capture(fn)
         r_ = g_.replay if g_ is not None else fn
         for _ in range(a.warmup):
             r_()
@@ -533,7 +568,7 @@ def main():
     # ---- communication overlap: the serial step beside the two-micro-batch step, and each of them
     # with the all-reduces dropped (numerically meaningless, timing only): exposed communication = step - that
     overlap = None
-    if tbo or world > 1:
+    if a.full and (tbo or world > 1):
         try:
             overlap = {"mode": ("two micro-batches of %d requests, one HIP stream and one native all-reduce communicator "
                                 "each: the all-reduce of one half runs beside the attention / GEMMs of the other" % (B // 2))
@@ -560,10 +595,10 @@ def main():
     # (models/llama.py:245-268: norm -> qkv_proj.apply -> rope -> attn.forward -> o_proj.apply -> norm -> gate_up.apply
     # -> act -> down.apply): no fused linear+consumer entry points, no producer-side fp8 quantisation
     plugin_only = None
-    if not a.no_plugin_surface:
+    if a.full and not a.no_plugin_surface:
         try:
             H.LlamaStack.fuse_decode_layer, H.Linear.fuse_producer_quant = False, False
-            g2 = capture(serial_step)
+            g2, _ = capture(serial_step)
             run2 = g2.replay if g2 is not None else serial_step
             for _ in range(a.warmup):
                 run2()
@@ -585,12 +620,11 @@ def main():
 
     # ---- roofline of the dominant kernel (decode attention), measured live with HIP events
     Hq, Hkv, D = stack.Hq, stack.Hkv, shape.head_dim
-    t_attn = time_attention_kernel(stack, runner, backend, fb, a.kernel_reps)
     abytes = attention_bytes(B, S, Hkv, D, Hq, kv_esize=1 if kv8 else 2)
-    achieved = abytes / t_attn / 1e9
+    t_attn = time_attention_kernel(stack, runner, backend, fb, a.kernel_reps) if a.full else None
     traffic = None
     tpath = os.path.join(ROOT, "profiles", "decode_attn_traffic.json")
-    if os.path.exists(tpath):
+    if a.full and os.path.exists(tpath):
         try:
             tj = json.load(open(tpath))
             if tj.get("batch") == B and tj.get("seq") == S and tj.get("tp") == tp and not kv8:
@@ -601,13 +635,13 @@ def main():
                                   + 3 * stack.inter * shape.hidden) + stack.vocab_shard * shape.hidden * 2)
     kv_splits = backend.forward_metadata.num_kv_splits
     prefill = None
-    if a.prefill_batch > 0:
+    if a.full and a.prefill_batch > 0:
         try:
             prefill = prefill_leg(H, stack, runner, backend, shape, a.prefill_batch, S, dev, world, chunk=a.prefill_chunk)
         except Exception as e:   # the decode number must not be lost to a prefill-side problem
             prefill = {"error": f"{type(e).__name__}: {e}"}
     ragged = None
-    if world == 1:
+    if a.full and world == 1:
         try:
             ragged = ragged_attention_leg(H, stack, runner, backend, B, S, dev)
         except Exception as e:   # informational only
@@ -618,7 +652,8 @@ def main():
                      f" [variant: {shape.name}, batch {B}, KV seq {S}" + (f", {a.layers} layers" if a.layers else "") + "]"),
         "value": round(tokens_per_s, 1), "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "median_synced_ms": round(median_ms, 4), "tokens_per_s_median_synced": round(B / (median_ms * 1e-3), 1),
+        "median_synced_ms": median_ms and round(median_ms, 4),
+        "tokens_per_s_median_synced": median_ms and round(B / (median_ms * 1e-3), 1),
         "plugin_surface_only": plugin_only,
         "overlap": overlap,
         "scaling": "strong" if world > 1 else "weak", "vs_baseline": None, "dtype": "fp8_e4m3 x fp8_e4m3 -> f32 (linears), " + ("fp8 e4m3" if kv8 else "bf16") + " KV/f32 softmax (attention)",
@@ -635,11 +670,12 @@ def main():
         "prefill": prefill,
         "ragged_decode_attention": ragged,
         "step_hbm_roofline_frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-        "roofline": {"kernel": "decode_attn_kernel (+ split merge)", "bound": "hbm", "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "algorithmic_bytes_per_launch": abytes, "avg_launch_us": round(t_attn * 1e6, 2)},
+        "roofline": t_attn and {"kernel": "decode_attn_kernel (+ split merge)", "bound": "hbm",
+                                "achieved": round(abytes / t_attn / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(abytes / t_attn / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic,
+                                "algorithmic_bytes_per_launch": abytes, "avg_launch_us": round(t_attn * 1e6, 2)},
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline({"llama3-8b": H.LLAMA3_8B, "llama3-70b": H.LLAMA3_70B}[a.model], B, S)
     elif rank == 0:
         result["cpu_baseline"] = None

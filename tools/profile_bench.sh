@@ -4,6 +4,7 @@
 set -o pipefail
 tag=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}
+set -- --full "$@"    # the trace covers every leg of the benchmark (roofline passes, plugin-surface step, ragged attention)
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $root/gpurun_out/$tag -- \
     python3 $root/bench.py --steps 5 --warmup 1 --no-cpu-baseline --prefill-batch 0 "$@" > $root/gpurun_out/$tag.log 2>&1

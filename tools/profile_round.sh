@@ -19,9 +19,10 @@ tools/pmc_attn.sh $tag
 cp profiles/decode_attn_traffic.json profiles/${tag}_decode_attn_pmc_fetch.csv profiles/${tag}_decode_attn_pmc_write.csv $out/ 2>/dev/null
 # the same command with one 16-sequence prefill chunk: per-kernel prefill times
 rm -rf gpurun_out/prof_${tag}_prefill
+prefill_log=$root/$(dirname $out)/prof_${tag}_prefill.log
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $root/gpurun_out/prof_${tag}_prefill -- \
-    python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-plugin-surface --prefill-batch 16 > $root/gpurun_out/prof_${tag}_prefill.log 2>&1
+    python3 $root/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-plugin-surface --prefill-batch 16 > $prefill_log 2>&1
 cd $root
 f=$(find gpurun_out/prof_${tag}_prefill -name "*kernel_trace.csv" | head -1)
 python3 tools/prof_summary.py "$f" 45 > $out/${tag}_bench_with_prefill_kernel_by_grid.txt

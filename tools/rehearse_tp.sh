@@ -8,4 +8,4 @@ set -o pipefail
 n=$1; shift
 export MI_BENCH_SAME_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 29517 \
-  bench.py --gpus $n --dist-backend gloo --steps 5 --warmup 2 --no-cpu-baseline --prefill-batch 0 --no-plugin-surface "$@"
+  bench.py --full --gpus $n --dist-backend gloo --steps 5 --warmup 2 --no-cpu-baseline --prefill-batch 0 --no-plugin-surface "$@"
