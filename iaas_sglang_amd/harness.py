@@ -146,8 +146,9 @@ class LlamaStack:
     then final norm + lm_head.  `make_method()` returns a fresh LinearMethodBase per linear."""
 
     def __init__(self, shape: ModelShape, make_method, dtype, device, tp=1, rank=0, group=None,
-                 weight_range=1e-3, seed=1234, weights_cpu_seeded=False, custom_ar=None):
+                 weight_range=1e-3, seed=1234, weights_cpu_seeded=False, custom_ar=None, native_lm_head=False):
         self.shape, self.dtype, self.device = shape, dtype, device
+        self.native_lm_head = native_lm_head    # lm_head through ops.bf16_gemm instead of the library GEMM (opt-in)
         self.tp, self.rank, self.group, self.custom_ar = tp, rank, group, custom_ar
         s = shape
         self.Hq, self.Hkv = s.num_heads // tp, max(1, s.num_kv_heads // tp)
@@ -189,6 +190,13 @@ class LlamaStack:
         # the cache as RotaryEmbedding.forward_native uses it (cast to the activation dtype per call,
         # rotary_embedding.py:150-151): the fused prefill forms read this copy
         self.cos_sin_t = self.cos_sin.to(dtype).contiguous()
+
+    def _lm_head(self, x):
+        """[M, hidden] -> [M, vocab shard] in the model dtype: the library GEMM, or with native_lm_head the 16-bit
+        decode kernel (M <= 512; a larger batch is an error, not a detour through the library)."""
+        if self.native_lm_head:
+            return ops.bf16_gemm(x, self.lm_head)
+        return torch.matmul(x, self.lm_head.t())
 
     @staticmethod
     def _init_linear(lin, dummy):
@@ -300,7 +308,7 @@ class LlamaStack:
             last = i + 1 == len(self.layers)
             nw = self.final_norm if last else self.layers[i + 1].input_norm
             x = L.down.quant_method.apply_add_rmsnorm16(L.down, act, residual, nw, s.rms_eps)
-        logits = torch.matmul(x, self.lm_head.t())
+        logits = self._lm_head(x)
         return tensor_model_parallel_all_gather(logits, self.tp, self.group)
 
     def forward_decode_fused(self, hidden, positions, fb, backend, return_hidden=False):
@@ -343,7 +351,7 @@ class LlamaStack:
                 x, qx = self._row_parallel_add_norm(L.down, act8, residual, nw, ns)
         if return_hidden:          # final-norm output; the caller runs the lm_head (two-micro-batch step: once, after the join)
             return x
-        logits = torch.matmul(x, self.lm_head.t())
+        logits = self._lm_head(x)
         return tensor_model_parallel_all_gather(logits, self.tp, self.group)
 
     def forward_decode_two_batch(self, hidden, positions, fbs, backends, streams, custom_ars=None, return_hidden=False):
@@ -393,7 +401,7 @@ class LlamaStack:
             o.record_stream(cur)       # allocated on a side stream, consumed on the joined one
         if return_hidden:              # final-norm output of the whole batch (tests capture the step without the lm_head)
             return torch.cat(outs, dim=0)
-        logits = torch.matmul(torch.cat(outs, dim=0), self.lm_head.t())
+        logits = self._lm_head(torch.cat(outs, dim=0))
         return tensor_model_parallel_all_gather(logits, self.tp, self.group)
 
     def forward(self, hidden, positions, fb, backend, last_token_logits=None):
@@ -463,7 +471,7 @@ class LlamaStack:
         x = ops.rmsnorm(hidden, self.final_norm, s.rms_eps, residual=residual)
         if last_token_logits is not None:
             x = x[torch.cumsum(last_token_logits.to(torch.int64), 0) - 1]
-        logits = torch.matmul(x, self.lm_head.t())
+        logits = self._lm_head(x)
         return tensor_model_parallel_all_gather(logits, self.tp, self.group)   # logits_processor.py:464-477
 
 

@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from ._lib import (MI_BF16, MI_FP16, MI_SCALE_ROW, MI_SCALE_TENSOR, MI_W4_AWQ, MI_W4_GPTQ,
+from ._lib import (MI_BF16, MI_F32, MI_FP16, MI_SCALE_ROW, MI_SCALE_TENSOR, MI_W4_AWQ, MI_W4_GPTQ,
                    MiHotpathError, check, lib)
 
 FP8_DTYPE = torch.float8_e4m3fn  # gfx950 = OCP e4m3fn
@@ -519,6 +519,49 @@ def fp8_gemm(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_b
     check(lib.mi_fp8_gemm(_ptr(a), _ptr(b_kn), _ptr(scale_a), _ptr(scale_b), _ptr(bias), _ptr(out), M, N, K,
                           a.stride(0), b_kn.stride(1), out.stride(0), sa_mode, sb_mode, _DT[out_dtype],
                           _ptr(ws), ws_bytes if ws is not None else 0, _stream()), "mi_fp8_gemm")
+    return out
+
+
+# -------------------------------------------------------------------------- bf16 / fp16
+def _out_code(x: torch.Tensor, out_dtype: torch.dtype) -> int:
+    assert out_dtype in (x.dtype, torch.float32), "out is the dtype of x or fp32"
+    return MI_F32 if out_dtype == torch.float32 else _dt(x)
+
+
+def bf16_gemm_ok(M: int, N: int, K: int, x: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> bool:
+    """Does the native 16-bit decode GEMM take this call?  The library answers: from the shape alone
+    (mi_bf16_gemm_workspace_bytes < 0: unsupported), and with the tensors given also for their strides, alignment
+    and offset range (mi_bf16_gemm_check, the function mi_bf16_gemm itself starts with)."""
+    if lib.mi_bf16_gemm_workspace_bytes(M, N, K) < 0:
+        return False
+    if x is None:
+        return True
+    if x.stride(-1) != 1 or weight.stride(-1) != 1 or (out is not None and out.stride(-1) != 1):
+        return False
+    # without `out` the call allocates a fresh [M,N] one: aligned, ldo = N (the check reads no memory)
+    po, ldo, od = (16, N, x.dtype) if out is None else (_ptr(out), out.stride(0), out.dtype)
+    return lib.mi_bf16_gemm_check(_ptr(x), _ptr(weight), po, M, N, K, x.stride(0), weight.stride(0), ldo,
+                                  _dt(x), _out_code(x, od)) == 0
+
+
+def bf16_gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [M,K] . weight [N,K]^T (+ bias) for decode batches (M <= 512): x, weight and bias all bf16 or all fp16,
+    weight in the torch.nn.Linear layout; out in that dtype (default) or fp32.  x and out may be row-strided."""
+    (M, K), (N, K2) = x.shape, weight.shape
+    assert K == K2 and x.dtype == weight.dtype
+    assert x.stride(1) == 1 and weight.stride(1) == 1, "rows of x and weight are contiguous"
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype or x.dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and (out_dtype is None or out.dtype == out_dtype)
+    if bias is not None:
+        assert bias.dtype == x.dtype and bias.numel() == N and bias.is_contiguous()
+    ws_bytes = max(lib.mi_bf16_gemm_workspace_bytes(M, N, K), 0)      # (< 0: the call below reports why)
+    ws = _gemm_workspace(ws_bytes, x.device) if ws_bytes else None
+    check(lib.mi_bf16_gemm(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), M, N, K, x.stride(0), weight.stride(0),
+                           out.stride(0), _dt(x), _out_code(x, out.dtype), _ptr(ws), ws_bytes, _stream()),
+          "mi_bf16_gemm")
     return out
 
 

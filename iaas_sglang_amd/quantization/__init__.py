@@ -7,6 +7,7 @@ from .compressed_tensors import CompressedTensorsConfig, CompressedTensorsLinear
 from .fp8 import Fp8Config, Fp8LinearMethod, apply_fp8_linear
 from .gptq import GPTQConfig, GPTQLinearMethod
 from .kv_cache import BaseKVCacheMethod, Fp8KVCacheMethod, kv_cache_scales_loader, load_kv_cache_scales
+from .unquantized import MiUnquantizedLinearMethod
 
 MI_QUANTIZATION_METHODS = {"fp8": Fp8Config, "awq": AWQConfig, "gptq": GPTQConfig,
                            "compressed-tensors": CompressedTensorsConfig}
@@ -14,4 +15,4 @@ MI_QUANTIZATION_METHODS = {"fp8": Fp8Config, "awq": AWQConfig, "gptq": GPTQConfi
 __all__ = ["Fp8Config", "Fp8LinearMethod", "apply_fp8_linear", "AWQConfig", "AWQLinearMethod",
            "GPTQConfig", "GPTQLinearMethod", "CompressedTensorsConfig", "CompressedTensorsLinearMethod",
            "CompressedTensorsW8A8Fp8", "BaseKVCacheMethod", "Fp8KVCacheMethod", "kv_cache_scales_loader",
-           "load_kv_cache_scales", "MI_QUANTIZATION_METHODS"]
+           "load_kv_cache_scales", "MiUnquantizedLinearMethod", "MI_QUANTIZATION_METHODS"]

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 9
+#define MI_ABI_VERSION 10
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -331,6 +331,29 @@ int mi_fp8_gemm(const void* a, const void* b_nk, const float* scale_a, const flo
 /* bytes of split-K scratch mi_fp8_gemm can use for this shape (0: none needed).  Passing less
  * (or null) is always correct, only slower for small-N decode shapes. */
 int64_t mi_fp8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+
+/* ------------------------------------------------ unquantised 16-bit linear (decode-shaped) */
+
+/* out[M,N] = x[M,K] . W[N,K]^T (+ bias), fp32 accumulate, out = round_once(acc + float(bias)).
+ *   x [M,K] (lda) and w_nk [N,K] (ldb, the torch.nn.Linear layout) both `dtype`; out (ldo) is `dtype` or MI_F32
+ *   (logits without a 16-bit rounding in between).  One pass covers 256 rows and streams the weights once;
+ *   257..512 rows run as two passes.
+ *   MI_ERR_UNSUPPORTED unless K % 64 == 0, lda % 8 == 0, ldb % 8 == 0, M <= 512 (prefill-shaped 16-bit GEMMs are
+ *   not this kernel), x / w_nk / out 16-byte aligned and (N-1)*ldb*2 + 256 < 2^32, (M-1)*lda*2 + 256 < 2^32
+ *   (32-bit lane offsets).  A null or too-small workspace is always correct: the call then runs without split-K.
+ * replaces: UnquantizedLinearMethod.apply (F.linear), layers/linear.py:152-193, for decode batches, and the
+ * lm_head matmul of LogitsProcessor._get_logits, layers/logits_processor.py:423-480. */
+int mi_bf16_gemm(const void* x, const void* w_nk, const void* bias /* nullable, dtype of x */, void* out,
+                 int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldo,
+                 int dtype /* MI_BF16 | MI_FP16 */, int out_dtype /* dtype | MI_F32 */,
+                 void* workspace /* nullable */, int64_t workspace_bytes, void* stream);
+/* bytes of split-K scratch mi_bf16_gemm can use for this shape (0: none needed); negative: the shape itself
+ * (K % 64, M > 512) is unsupported. */
+int64_t mi_bf16_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+/* every precondition of mi_bf16_gemm, strides and alignment included, without a launch: MI_OK exactly when the
+ * same arguments are accepted there (mi_bf16_gemm itself starts with this call). */
+int mi_bf16_gemm_check(const void* x, const void* w_nk, const void* out, int64_t M, int64_t N, int64_t K,
+                       int64_t lda, int64_t ldb, int64_t ldo, int dtype, int out_dtype);
 
 /* -------------------------------------------------------- int4 weight-only GEMM */
 
