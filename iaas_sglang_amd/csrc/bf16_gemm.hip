@@ -287,6 +287,21 @@ void launch_rows(const HalfGemm& p, hipStream_t st) {
 
 }  // namespace
 
+// the slab reduction on its own, for the prefill tile kernel (bf16_gemm_tile.hip), whose slabs have the same form
+MI_INTERNAL void mi_bf16_gemm_reduce(float* slab, const void* bias, void* out, int64_t M, int64_t N, int64_t ldo, int S,
+                                     int dtype, int out_dtype, hipStream_t st) {
+  HalfGemm p = {};
+  p.bias = bias; p.out = out; p.slab = slab; p.M = M; p.N = N; p.ldo = ldo; p.S = S;
+  const unsigned blocks = (unsigned)cdiv64(M * cdiv64(N, 4), 256);
+  if (dtype == MI_BF16) {
+    if (out_dtype == MI_F32) bf16_gemm_reduce_kernel<bf16_t, float><<<blocks, 256, 0, st>>>(p);
+    else bf16_gemm_reduce_kernel<bf16_t, bf16_t><<<blocks, 256, 0, st>>>(p);
+  } else {
+    if (out_dtype == MI_F32) bf16_gemm_reduce_kernel<f16_t, float><<<blocks, 256, 0, st>>>(p);
+    else bf16_gemm_reduce_kernel<f16_t, f16_t><<<blocks, 256, 0, st>>>(p);
+  }
+}
+
 extern "C" int64_t mi_bf16_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M < 0 || N < 0 || K <= 0 || shape_refusal(M, N, K)) return -1;
   if (M == 0 || N == 0) return 0;

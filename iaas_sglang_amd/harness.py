@@ -193,9 +193,9 @@ class LlamaStack:
 
     def _lm_head(self, x):
         """[M, hidden] -> [M, vocab shard] in the model dtype: the library GEMM, or with native_lm_head the 16-bit
-        decode kernel (M <= 512; a larger batch is an error, not a detour through the library)."""
+        decode kernel up to 512 rows and the 16-bit tile kernel beyond (never a detour through the library)."""
         if self.native_lm_head:
-            return ops.bf16_gemm(x, self.lm_head)
+            return ops.bf16_gemm(x, self.lm_head) if x.shape[0] <= 512 else ops.bf16_gemm_tile(x, self.lm_head)
         return torch.matmul(x, self.lm_head.t())
 
     @staticmethod

@@ -565,6 +565,41 @@ def bf16_gemm(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor
     return out
 
 
+def bf16_gemm_tile_ok(M: int, N: int, K: int, x: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> bool:
+    """Does the native 16-bit prefill tile GEMM take this call?  As bf16_gemm_ok, answered by the library:
+    mi_bf16_gemm_tile_workspace_bytes for the shape, mi_bf16_gemm_tile_check for the tensors."""
+    if lib.mi_bf16_gemm_tile_workspace_bytes(M, N, K) < 0:
+        return False
+    if x is None:
+        return True
+    if x.stride(-1) != 1 or weight.stride(-1) != 1 or (out is not None and out.stride(-1) != 1):
+        return False
+    po, ldo, od = (16, N, x.dtype) if out is None else (_ptr(out), out.stride(0), out.dtype)
+    return lib.mi_bf16_gemm_tile_check(_ptr(x), _ptr(weight), po, M, N, K, x.stride(0), weight.stride(0), ldo,
+                                       _dt(x), _out_code(x, od)) == 0
+
+
+def bf16_gemm_tile(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16_gemm for prefill batches (any M; the linear method sends it M > 512): 256 x 256 output tiles on a
+    persistent grid.  Same operands, same rounding, same strides allowed."""
+    (M, K), (N, K2) = x.shape, weight.shape
+    assert K == K2 and x.dtype == weight.dtype
+    assert x.stride(1) == 1 and weight.stride(1) == 1, "rows of x and weight are contiguous"
+    if out is None:
+        out = torch.empty(M, N, dtype=out_dtype or x.dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and (out_dtype is None or out.dtype == out_dtype)
+    if bias is not None:
+        assert bias.dtype == x.dtype and bias.numel() == N and bias.is_contiguous()
+    ws_bytes = max(lib.mi_bf16_gemm_tile_workspace_bytes(M, N, K), 0)      # (< 0: the call below reports why)
+    ws = _gemm_workspace(ws_bytes, x.device) if ws_bytes else None
+    check(lib.mi_bf16_gemm_tile(_ptr(x), _ptr(weight), _ptr(bias), _ptr(out), M, N, K, x.stride(0), weight.stride(0),
+                                out.stride(0), _dt(x), _out_code(x, out.dtype), _ptr(ws), ws_bytes, _stream()),
+          "mi_bf16_gemm_tile")
+    return out
+
+
 # -------------------------------------------------------------------------- int4
 def w4_repack(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, group_size: int,
               layout: int, g_idx: Optional[torch.Tensor] = None):

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 10
+#define MI_ABI_VERSION 11
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -354,6 +354,27 @@ int64_t mi_bf16_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
  * same arguments are accepted there (mi_bf16_gemm itself starts with this call). */
 int mi_bf16_gemm_check(const void* x, const void* w_nk, const void* out, int64_t M, int64_t N, int64_t K,
                        int64_t lda, int64_t ldb, int64_t ldo, int dtype, int out_dtype);
+
+/* ------------------------------------------------ unquantised 16-bit linear (prefill-shaped) */
+
+/* The same product with the same arguments and the same rounding as mi_bf16_gemm, for any M >= 1: a persistent grid of
+ *   256 x 256 output tiles (bf16_gemm_tile.hip), meant for M > 512 where mi_bf16_gemm refuses.  Grids that leave half
+ *   the CUs idle split K into up to 4 slices of fp32 slabs in `workspace`, summed in split order by a reduce kernel.
+ *   MI_ERR_UNSUPPORTED unless K % 64 == 0, lda % 8 == 0, ldb % 8 == 0, x / w_nk / out 16-byte aligned,
+ *   255*lda*2 + 128 < 2^32 and 255*ldb*2 + 128 < 2^32 (32-bit lane offsets inside an operand block) and the tile count
+ *   fits the grid.  A null or too-small workspace is always correct: the call then runs without split-K.
+ * replaces: UnquantizedLinearMethod.apply (F.linear), layers/linear.py:152-193, for prefill batches. */
+int mi_bf16_gemm_tile(const void* x, const void* w_nk, const void* bias /* nullable, dtype of x */, void* out,
+                      int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldo,
+                      int dtype /* MI_BF16 | MI_FP16 */, int out_dtype /* dtype | MI_F32 */,
+                      void* workspace /* nullable */, int64_t workspace_bytes, void* stream);
+/* bytes of split-K scratch mi_bf16_gemm_tile can use for this shape (0: none needed); negative: the shape itself
+ * (K % 64) is unsupported. */
+int64_t mi_bf16_gemm_tile_workspace_bytes(int64_t M, int64_t N, int64_t K);
+/* every precondition of mi_bf16_gemm_tile, strides and alignment included, without a launch: MI_OK exactly when the
+ * same arguments are accepted there (mi_bf16_gemm_tile itself starts with this call). */
+int mi_bf16_gemm_tile_check(const void* x, const void* w_nk, const void* out, int64_t M, int64_t N, int64_t K,
+                            int64_t lda, int64_t ldb, int64_t ldo, int dtype, int out_dtype);
 
 /* -------------------------------------------------------- int4 weight-only GEMM */
 
