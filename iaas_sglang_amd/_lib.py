@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_hotpath.so")
 
-ABI_VERSION = 11         # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
+ABI_VERSION = 12         # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
 MI_BF16, MI_FP16, MI_F32 = 0, 1, 2
 MI_SCALE_TENSOR, MI_SCALE_ROW = 0, 1
 MI_W4_AWQ, MI_W4_GPTQ = 0, 1
@@ -58,6 +58,9 @@ SIGNATURES = {
     "mi_fp8_quant_per_token": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
     "mi_fp8_gemm": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _p, _i64, _p]),
     "mi_fp8_gemm_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "mi_int8_quant_per_token": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
+    "mi_int8_gemm": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p, _i64, _p]),
+    "mi_int8_gemm_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "mi_bf16_gemm": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _p, _i64, _p]),
     "mi_bf16_gemm_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "mi_bf16_gemm_check": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int]),

@@ -522,6 +522,44 @@ def fp8_gemm(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_b
     return out
 
 
+# -------------------------------------------------------------------------- int8 W8A8
+def int8_quant_per_token(x: torch.Tensor, out: Optional[torch.Tensor] = None,
+                         scales: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x bf16/fp16 [M,K] (rows may be strided) -> (q int8 [M,K], scales fp32 [M,1]); scales = absmax / 127."""
+    assert x.dim() == 2 and x.stride(1) == 1
+    M, K = x.shape
+    out = torch.empty(M, K, dtype=torch.int8, device=x.device) if out is None else out
+    scales = torch.empty(M, 1, dtype=torch.float32, device=x.device) if scales is None else scales
+    assert out.dtype == torch.int8 and out.shape == (M, K) and out.is_contiguous()
+    assert scales.dtype == torch.float32 and scales.numel() == M and scales.is_contiguous()
+    check(lib.mi_int8_quant_per_token(_ptr(x), _ptr(out), _ptr(scales), M, K, x.stride(0), _dt(x), _stream()),
+          "mi_int8_quant_per_token")
+    return out, scales
+
+
+def int8_gemm(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+              out_dtype: torch.dtype, bias: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a int8 [M,K]; b_kn int8 [K,N] *column-major* (the `.t()` view of [N,K] storage, as the reference stores it);
+    scale_a M values (per token), scale_b N values (per channel); out bf16 / fp16, any M >= 1."""
+    M, K = a.shape
+    K2, N = b_kn.shape
+    assert K == K2 and a.dtype == torch.int8 and b_kn.dtype == torch.int8
+    assert a.stride(1) == 1 and b_kn.stride(0) == 1, "b must be the [K,N] view of [N,K] row-major storage"
+    assert scale_a.dtype == torch.float32 and scale_a.numel() == M and scale_a.is_contiguous()
+    assert scale_b.dtype == torch.float32 and scale_b.numel() == N and scale_b.is_contiguous()
+    out = torch.empty(M, N, dtype=out_dtype, device=a.device) if out is None else out
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == out_dtype
+    if bias is not None:
+        assert bias.dtype == out_dtype and bias.numel() == N and bias.is_contiguous()
+    ws_bytes = max(lib.mi_int8_gemm_workspace_bytes(M, N, K), 0)      # (< 0: the call below reports why)
+    ws = _gemm_workspace(ws_bytes, a.device) if ws_bytes else None
+    check(lib.mi_int8_gemm(_ptr(a), _ptr(b_kn), _ptr(scale_a), _ptr(scale_b), _ptr(bias), _ptr(out), M, N, K,
+                           a.stride(0), b_kn.stride(1), out.stride(0), _DT[out_dtype], _ptr(ws), ws_bytes, _stream()),
+          "mi_int8_gemm")
+    return out
+
+
 # -------------------------------------------------------------------------- bf16 / fp16
 def _out_code(x: torch.Tensor, out_dtype: torch.dtype) -> int:
     assert out_dtype in (x.dtype, torch.float32), "out is the dtype of x or fp32"

@@ -11,7 +11,7 @@ registration wraps those seams without editing any reference file (SURVEY sectio
        schedule_batch.write_req_to_token_pool_triton[(bs,)](...), schedule_batch.get_last_loc_triton,
        forward_batch_info.compute_position_triton  (support_triton() stays True for our backend name, so the
        scheduler takes its one-launch branch instead of the per-request python loop, schedule_batch.py:1290-1309)
-  4. QUANTIZATION_METHODS["fp8"|"awq"|"gptq"] -> our configs; awq/gptq are moved out of the
+  4. QUANTIZATION_METHODS["fp8"|"awq"|"gptq"|"w8a8_int8"] -> our configs; awq/gptq are moved out of the
      vllm-gated table (quantization/__init__.py:75-120)
 
 Usage (in the process that launches the server, before arguments are parsed):
@@ -67,8 +67,8 @@ def register(override_quantization: bool = True) -> bool:
     if override_quantization:
         import sglang.srt.layers.quantization as q
 
-        from .quantization import MI_QUANTIZATION_METHODS
-        for name, cfg in MI_QUANTIZATION_METHODS.items():
+        from .quantization import MI_EXTRA_QUANTIZATION_METHODS, MI_QUANTIZATION_METHODS
+        for name, cfg in {**MI_QUANTIZATION_METHODS, **MI_EXTRA_QUANTIZATION_METHODS}.items():
             q.QUANTIZATION_METHODS[name] = cfg
             q.BASE_QUANTIZATION_METHODS[name] = cfg
             q.VLLM_QUANTIZATION_METHODS.pop(name, None)

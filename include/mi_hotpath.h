@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 11
+#define MI_ABI_VERSION 12
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -375,6 +375,37 @@ int64_t mi_bf16_gemm_tile_workspace_bytes(int64_t M, int64_t N, int64_t K);
  * same arguments are accepted there (mi_bf16_gemm_tile itself starts with this call). */
 int mi_bf16_gemm_tile_check(const void* x, const void* w_nk, const void* out, int64_t M, int64_t N, int64_t K,
                             int64_t lda, int64_t ldb, int64_t ldo, int dtype, int out_dtype);
+
+/* ------------------------------------------------------------------ INT8 W8A8 */
+
+/* Per-token int8 quant.  x [M,K] bf16/fp16 (row stride ldx elements), q int8 [M,K] contiguous, scales fp32 [M]:
+ *   absmax = max(max_k |x[m,k]|, 1e-10); scales[m] = absmax / 127 (IEEE divide);
+ *   q = round(x * (127 / absmax)) in fp32, ties away from zero -- always in [-127, 127]; an all-zero row gives q = 0.
+ *   `127 / absmax` as torch evaluates it: fp32(fp32(1 / absmax) * 127).
+ *   MI_ERR_UNSUPPORTED unless K % 8 == 0 and ldx % 8 == 0.
+ * replaces: per_token_quant_int8 as imported at quantization/w8a8_int8.py:14 (arithmetic restated at
+ * test/srt/cpu/utils.py:24-31). */
+int mi_int8_quant_per_token(const void* x, void* q, float* scales, int64_t M, int64_t K, int64_t ldx, int dtype,
+                            void* stream);
+
+/* out[m][n] = round_once(((float)acc * scale_a[m]) * scale_b[n] + (float)bias[n]),
+ *   acc = sum_k a[m][k] * b_nk[n][k] exact in int32 (this order of operations is the contract).
+ *   a int8 [M,K] row-major (lda), b_nk int8 stored [N,K] row-major (ldb) == the column-major [K,N] view the reference
+ *   passes (w8a8_int8.py:91 `weight.t()`); scale_a fp32 [M], scale_b fp32 [N]; bias out_dtype [N]; out bf16 / fp16.
+ *   Any M >= 1: up to 256 rows run the decode-shaped kernel (weights streamed once, split-K through int32 slabs in
+ *   `workspace`), more rows the 256 x 256 tile kernel.  Results do not depend on the workspace: int32 sums commute.
+ *   MI_ERR_UNSUPPORTED unless K % 64 == 0, K <= 131072 (the accumulator cannot wrap), lda % 16 == 0, ldb % 16 == 0,
+ *   a / b_nk / out 16-byte aligned and the 32-bit lane offsets hold: M <= 256: (M-1)*lda + 128 < 2^32 and
+ *   (N-1)*ldb + 128 < 2^32; M > 256: 255*lda + 128 < 2^32 and (min(N,256)-1)*ldb + 128 < 2^32.
+ *   A null or too-small workspace is always correct: the call then runs without split-K.
+ * replaces: int8_scaled_mm, sgl-kernel/csrc/gemm/int8_gemm_kernel.cu (CUDA only), as called at w8a8_int8.py:136-145. */
+int mi_int8_gemm(const void* a, const void* b_nk, const float* scale_a, const float* scale_b,
+                 const void* bias /* nullable, out_dtype */, void* out, int64_t M, int64_t N, int64_t K, int64_t lda,
+                 int64_t ldb, int64_t ldo, int out_dtype /* MI_BF16 | MI_FP16 */, void* workspace /* nullable */,
+                 int64_t workspace_bytes, void* stream);
+/* bytes of split-K scratch mi_int8_gemm can use for this shape (0: none needed); negative: the shape itself
+ * (K % 64, K > 131072) is unsupported. */
+int64_t mi_int8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
 
 /* -------------------------------------------------------- int4 weight-only GEMM */
 
