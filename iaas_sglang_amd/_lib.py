@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_hotpath.so")
 
-ABI_VERSION = 12         # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
+ABI_VERSION = 13        # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
 MI_BF16, MI_FP16, MI_F32 = 0, 1, 2
 MI_SCALE_TENSOR, MI_SCALE_ROW = 0, 1
 MI_W4_AWQ, MI_W4_GPTQ = 0, 1
@@ -61,7 +61,13 @@ SIGNATURES = {
     "mi_int8_quant_per_token": (_int, [_p, _p, _p, _i64, _i64, _i64, _int, _p]),
     "mi_int8_gemm": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p, _i64, _p]),
     "mi_int8_gemm_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "mi_bf16_gemm": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _p, _i64, _p]),
+    "mi_rmsnorm_int8": (_int, [_p] * 6 + [_i64] * 5 + [_f, _int, _p]),
+    "mi_silu_and_mul_int8": (_int, [_p] * 4 + [_i64] * 4 + [_int, _p]),
+    "mi_int8_gemm_fused_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "mi_int8_gemm_add_rmsnorm_int8": (_int, [_p] * 9 + [_i64] * 5 + [_f, _int, _p, _i64, _p]),
+    "mi_int8_gemm_rope_kvwrite": (_int, [_p] * 10 + [_i64] * 10 + [_int, _p, _i64, _p]),
+    "mi_int8_gemm_silu_mul_int8": (_int, [_p] * 6 + [_i64] * 5 + [_int, _p, _i64, _p]),
+    "mi_bf16_gemm": (_int,[_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _p, _i64, _p]),
     "mi_bf16_gemm_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "mi_bf16_gemm_check": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int]),
     "mi_bf16_gemm_tile": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _p, _i64, _p]),

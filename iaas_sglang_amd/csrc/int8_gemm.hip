@@ -27,7 +27,8 @@
 //                ask for the same 128-byte column of every activation row at once.
 //   epilogue     the consumers park the int32 tile in the (drained) ring, rows padded to 528 bytes, and all 8 waves
 //                write whole rows: the scaled, biased, once-rounded result to `out` when S == 1, else raw int32 into
-//                slab[s][m][n]; int8_gemm_reduce_kernel sums the slabs (exactly) and applies the same epilogue.
+//                slab[s][m][n]; int8_gemm_reduce_kernel sums the slabs (exactly) and applies the same epilogue.  The
+//                partial launch of the fused forms (bottom of the file, int8_glue.hip) always takes the slab branch.
 //
 // int8_gemm_tile_kernel (M > 256): one 512-thread workgroup per 256 x 256 output tile, wave (wm, wn) of the 2 x 4 wave
 //   grid owns 128 x 64.  k-steps of 128 bytes; both operands go global -> LDS by LDS-DMA into the same swizzled image,
@@ -67,6 +68,7 @@ struct Int8Gemm {
   int32_t* slab;      // [S][M][N] when S > 1
   int64_t M, N, K, lda, ldb, ldo;
   int S, per;         // split-K slices, k-phases per slice
+  int raw;            // the decode kernel leaves raw int32 in slab[sp] (S > 1, or the partial launch of the fused forms)
 };
 
 __device__ __forceinline__ i32x4 mfma_i8(const uint4& a, const uint4& b, i32x4 c) {
@@ -239,7 +241,7 @@ __global__ __launch_bounds__(512) void int8_gemm_kernel(const Int8Gemm p) {
   const int c = (lane & 31) * 4;
   const int64_t n0 = n_blk + c;
   if (n0 >= p.N) return;
-  const bool to_slab = p.S > 1;
+  const bool to_slab = p.raw != 0;
   const bool full4 = n0 + 3 < p.N;
   const bool has_bias = p.bias != nullptr;
   float bv[4] = {0.f, 0.f, 0.f, 0.f}, sbv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -465,7 +467,7 @@ template <typename OutT, int MT>
 void launch_decode(const Int8Gemm& p, hipStream_t st) {
   const dim3 grid((unsigned)cdiv64(p.N, kBlockCols), (unsigned)p.S);
   int8_gemm_kernel<OutT, MT><<<grid, 512, ring_bytes<MT>(), st>>>(p);
-  if (p.S > 1) {
+  if (p.S > 1 && p.out != nullptr) {             // (the partial launch has no `out`: its caller consumes the slabs)
     const int64_t total = p.M * cdiv64(p.N, 4);
     int8_gemm_reduce_kernel<OutT><<<(unsigned)cdiv64(total, 256), 256, 0, st>>>(p);
   }
@@ -526,9 +528,36 @@ extern "C" int mi_int8_gemm(const void* a, const void* b_nk, const float* scale_
     p.S = 1;
     p.per = (int)cdiv64(K, kPhaseBytes);
   }
+  p.raw = p.S > 1;
   hipStream_t st = (hipStream_t)stream;
   if (out_dtype == MI_BF16) launch<bf16_t>(p, st);
   else launch<f16_t>(p, st);
+  MI_CHECK_LAUNCH();
+  return MI_OK;
+}
+
+// ---- hooks of the fused "GEMM + consumer" forms (int8_glue.hip); not part of the C ABI
+MI_INTERNAL void mi_int8_gemm_plan_splits(int64_t N, int64_t K, int* S, int* per) { plan_splits(N, K, S, per); }
+
+// The decode kernel alone (M <= 256): raw int32 accumulators into slab[S][M][N], S = the plan's, also when S == 1; no
+// reduce, no scales.  Same operand preconditions as mi_int8_gemm; N % 4 == 0 and a 16-byte aligned slab on top.
+MI_INTERNAL int mi_int8_gemm_partial(const void* a, const void* b_nk, int32_t* slab, int64_t M, int64_t N, int64_t K,
+                                     int64_t lda, int64_t ldb, void* stream) {
+  MI_CHECK_ARG(M > 0 && M <= kPassRows && N > 0 && N % 4 == 0 && K > 0 && a && b_nk && slab);
+  MI_CHECK_ARG(lda >= K && ldb >= K && ((uintptr_t)slab & 15) == 0);
+  if (const char* why = shape_refusal(M, N, K))
+    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_int8_gemm (fused): %s (M %lld N %lld K %lld)", why, (long long)M, (long long)N, (long long)K);
+  if (lda % 16 != 0 || ldb % 16 != 0 || (((uintptr_t)a | (uintptr_t)b_nk) & 15) != 0)
+    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_int8_gemm (fused): a and b_nk must be 16-byte aligned, lda and ldb multiples of 16");
+  if ((uint64_t)(M - 1) * (uint64_t)lda + kPhaseBytes >= (1ull << 32) || (uint64_t)(N - 1) * (uint64_t)ldb + kPhaseBytes >= (1ull << 32))
+    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_int8_gemm (fused): operand rows span 4 GiB or more (32-bit lane offsets)");
+  Int8Gemm p;
+  p.a = (const uint8_t*)a; p.b = (const uint8_t*)b_nk; p.sa = nullptr; p.sb = nullptr; p.bias = nullptr; p.out = nullptr;
+  p.slab = slab;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldo = N;
+  plan_splits(N, K, &p.S, &p.per);
+  p.raw = 1;
+  launch<bf16_t>(p, (hipStream_t)stream);      // OutT only types the epilogue this launch does not take
   MI_CHECK_LAUNCH();
   return MI_OK;
 }

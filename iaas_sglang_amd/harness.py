@@ -168,6 +168,7 @@ class LlamaStack:
 
         def linear(k, outs):
             lin = Linear(k, outs, make_method(), dtype).to(device)
+            lin.dummy_weight_range = weight_range
             self._init_linear(lin, dummy)
             lin.quant_method.process_weights_after_loading(lin)
             return lin
@@ -206,6 +207,11 @@ class LlamaStack:
             w = names["weight"]
             if w.dtype in (torch.bfloat16, torch.float16):   # fp8 from a bf16 checkpoint: plain weight
                 w.data.copy_(dummy(*w.shape))
+            elif w.dtype == torch.int8:                      # W8A8 int8 checkpoint: full-range int8 + per-channel scales
+                g = torch.Generator(device=w.device).manual_seed(1234)
+                w.data.copy_(torch.randint(-128, 128, w.shape, dtype=torch.int8, device=w.device, generator=g))
+                # dequantised weights span the dummy range (the stack's weight_range, noted on the module by linear())
+                names["weight_scale"].data.fill_(getattr(lin, "dummy_weight_range", 1e-3) / 127.0)
             else:                                            # serialized FP8 checkpoint: fp8 weight + scales
                 qw, ws = ops.fp8_quant_per_tensor(dummy(*w.shape), weight_mode=True)
                 w.data.copy_(qw)
@@ -311,6 +317,48 @@ class LlamaStack:
         logits = self._lm_head(x)
         return tensor_model_parallel_all_gather(logits, self.tp, self.group)
 
+    def _int8_producers(self):
+        """W8A8 int8 linears throughout, and producer fusion on: norm / activation kernels emit int8 + per-token scales."""
+        if not (LlamaStack.fuse_decode_layer and Linear.fuse_producer_quant) or Linear.calibrating:
+            return False
+        return all(hasattr(lin.quant_method, "fused_decode8_ok")
+                   for L in self.layers for lin in (L.qkv, L.o, L.gate_up, L.down))
+
+    def _fused_decode8_ok(self, hidden, fb):
+        """W8A8 int8 linears: every linear has the fused-consumer forms at this batch size (one pass of the int8 decode
+        kernel), TP = 1, and the KV pool holds the activation dtype."""
+        M = hidden.shape[0]
+        if not self._int8_producers() or self.tp != 1 or not fb.forward_mode.is_decode() or M > 256:
+            return False
+        if fb.token_to_kv_pool.get_key_buffer(0).dtype != self.dtype:
+            return False
+        return all(lin.quant_method.fused_decode8_ok(lin, M)
+                   for L in self.layers for lin in (L.qkv, L.o, L.gate_up, L.down))
+
+    def forward_decode_fused8(self, hidden, positions, fb, backend):
+        """The layer sequence of forward() for W8A8 int8 linears, each linear fused with its consumer and every
+        consumer emitting the next linear's int8 activation + per-token scales: norm+quant (first layer) |
+        qkv + rope + kv-write | attention | quant | o + add + norm + quant | gate_up + silu*mul + quant |
+        down + add + norm(next layer) + quant -- 10 launches per layer (+ the split merge) instead of 17, bit-identical."""
+        s, D = self.shape, self.shape.head_dim
+        pool = fb.token_to_kv_pool
+        residual = hidden
+        xq, xs, _ = ops.rmsnorm_int8(hidden, self.layers[0].input_norm, s.rms_eps)
+        x = None
+        for i, L in enumerate(self.layers):
+            q = L.qkv.quant_method.apply_rope_kvwrite8(L.qkv, xq, xs, positions, self.cos_sin, pool.get_key_buffer(i),
+                                                       pool.get_value_buffer(i), fb.out_cache_loc, self.Hq, self.Hkv, D)
+            a = backend.forward(q, None, None, L.attn, fb, save_kv_cache=False)
+            aq, a_s = ops.int8_quant_per_token(a)
+            _, xq, xs = L.o.quant_method.apply_add_rmsnorm8(L.o, aq, a_s, residual, L.post_norm, s.rms_eps)
+            actq, act_s = L.gate_up.quant_method.apply_silu_mul8(L.gate_up, xq, xs, self.dtype)
+            last = i + 1 == len(self.layers)
+            nw = self.final_norm if last else self.layers[i + 1].input_norm
+            x, xq, xs = L.down.quant_method.apply_add_rmsnorm8(L.down, actq, act_s, residual, nw, s.rms_eps,
+                                                               want_q=not last, want_out=last)
+        logits = self._lm_head(x)
+        return tensor_model_parallel_all_gather(logits, self.tp, self.group)
+
     def forward_decode_fused(self, hidden, positions, fb, backend, return_hidden=False):
         """The same layer sequence as forward() with each FP8 linear fused with its consumer:
         norm+quant | qkv+rope+kv-write | attention(+quant) | o+add+norm+quant | gate_up+silu*mul+quant |
@@ -413,6 +461,9 @@ class LlamaStack:
             return self.forward_decode_fused(hidden, positions, fb, backend)
         if last_token_logits is None and self._fused_decode16_ok(hidden, fb):
             return self.forward_decode_fused16(hidden, positions, fb, backend)
+        if last_token_logits is None and self._fused_decode8_ok(hidden, fb):
+            return self.forward_decode_fused8(hidden, positions, fb, backend)
+        int8 = self._int8_producers()      # prefill / TP > 1: int8-emitting producers, the linears take (q, scales)
         residual = None
         for L in self.layers:
             first = residual is None
@@ -423,6 +474,9 @@ class LlamaStack:
                 qkv = L.qkv.forward_prequantized(
                     ops.rmsnorm_fp8(hidden, L.input_norm, s.rms_eps, qs, residual=None if first else residual),
                     self.dtype)
+            elif int8:
+                xq, xs, _ = ops.rmsnorm_int8(hidden, L.input_norm, s.rms_eps, residual=None if first else residual)
+                qkv = L.qkv.quant_method.apply_prequantized(L.qkv, xq, xs, self.dtype, L.qkv.bias)
             else:
                 x = ops.rmsnorm(hidden, L.input_norm, s.rms_eps, residual=None if first else residual)
                 qkv = L.qkv(x)
@@ -461,11 +515,17 @@ class LlamaStack:
             if qs is not None:
                 gu = L.gate_up.forward_prequantized(
                     ops.rmsnorm_fp8(hidden, L.post_norm, s.rms_eps, qs, residual=residual), self.dtype)
+            elif int8:
+                xq, xs, _ = ops.rmsnorm_int8(hidden, L.post_norm, s.rms_eps, residual=residual)
+                gu = L.gate_up.quant_method.apply_prequantized(L.gate_up, xq, xs, self.dtype, L.gate_up.bias)
             else:
                 gu = L.gate_up(ops.rmsnorm(hidden, L.post_norm, s.rms_eps, residual=residual))
             qs = L.down.fused_quant_scale()
             if qs is not None:
                 hidden = self._all_reduce(L.down.forward_prequantized(ops.silu_and_mul_fp8(gu, qs), self.dtype))
+            elif int8:
+                aq, a_s, _ = ops.silu_and_mul_int8(gu)
+                hidden = self._all_reduce(L.down.quant_method.apply_prequantized(L.down, aq, a_s, self.dtype, L.down.bias))
             else:
                 hidden = self._all_reduce(L.down(ops.silu_and_mul(gu)))
         x = ops.rmsnorm(hidden, self.final_norm, s.rms_eps, residual=residual)

@@ -560,6 +560,117 @@ def int8_gemm(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_
     return out
 
 
+def rmsnorm_int8(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None,
+                 want_out: bool = False):
+    """rmsnorm (+ in-place residual add) with the per-token int8 quantisation of the following linear fused in:
+    returns (q int8 [M,H], scales fp32 [M,1], out | None); bit-identical to rmsnorm() -> int8_quant_per_token()."""
+    assert x.dim() == 2 and x.stride(1) == 1 and weight.is_contiguous() and weight.dtype == x.dtype
+    M, H = x.shape
+    if residual is not None:
+        assert residual.shape == x.shape and residual.stride(1) == 1 and residual.dtype == x.dtype
+    q = torch.empty(M, H, dtype=torch.int8, device=x.device)
+    scales = torch.empty(M, 1, dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x) if want_out else None
+    check(lib.mi_rmsnorm_int8(_ptr(x), _ptr(residual), _ptr(weight), _ptr(out), _ptr(q), _ptr(scales), M, H, x.stride(0),
+                              residual.stride(0) if residual is not None else 0, out.stride(0) if want_out else 0,
+                              float(eps), _dt(x), _stream()), "mi_rmsnorm_int8")
+    return q, scales, out
+
+
+def silu_and_mul_int8(x: torch.Tensor, want_out: bool = False):
+    """silu(x[:, :I]) * x[:, I:] with the per-token int8 quantisation fused in: (q int8 [M,I], scales fp32 [M,1],
+    out | None); bit-identical to silu_and_mul() -> int8_quant_per_token()."""
+    assert x.dim() == 2 and x.stride(1) == 1 and x.shape[1] % 2 == 0
+    M, I = x.shape[0], x.shape[1] // 2
+    q = torch.empty(M, I, dtype=torch.int8, device=x.device)
+    scales = torch.empty(M, 1, dtype=torch.float32, device=x.device)
+    out = torch.empty(M, I, dtype=x.dtype, device=x.device) if want_out else None
+    check(lib.mi_silu_and_mul_int8(_ptr(x), _ptr(out), _ptr(q), _ptr(scales), M, I, x.stride(0),
+                                   out.stride(0) if want_out else 0, _dt(x), _stream()), "mi_silu_and_mul_int8")
+    return q, scales, out
+
+
+# ------------------------------------------- decode-shaped int8 linears fused with their consumer (M <= 256)
+def int8_fused_ok(M: int, N: int, K: int) -> bool:
+    return N % 8 == 0 and lib.mi_int8_gemm_fused_workspace_bytes(M, N, K) > 0
+
+
+def _int8_fused_ws(M: int, N: int, K: int, device):
+    nbytes = lib.mi_int8_gemm_fused_workspace_bytes(M, N, K)
+    if nbytes <= 0:
+        raise MiHotpathError(f"fused int8 linear: decode shapes only (M={M} <= 256, K={K} % 64 == 0)")
+    return _gemm_workspace(nbytes, device), nbytes
+
+
+def _check_int8_operands(a, b_kn, scale_a, scale_b):
+    assert a.dtype == torch.int8 and b_kn.dtype == torch.int8 and a.shape[1] == b_kn.shape[0]
+    assert a.stride(1) == 1 and b_kn.stride(0) == 1, "b must be the [K,N] view of [N,K] row-major storage"
+    assert scale_a.dtype == torch.float32 and scale_a.numel() == a.shape[0] and scale_a.is_contiguous()
+    assert scale_b.dtype == torch.float32 and scale_b.numel() == b_kn.shape[1] and scale_b.is_contiguous()
+
+
+def int8_gemm_add_rmsnorm(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                          residual: Optional[torch.Tensor], norm_weight: torch.Tensor, eps: float,
+                          want_q: bool = True, want_out: bool = False):
+    """y = rmsnorm(a.b * sa * sb (+ residual, updated in place)) * w; returns (out | None, q int8 | None, scales | None),
+    (q, scales) = per-token int8 of y for the next linear."""
+    _check_int8_operands(a, b_kn, scale_a, scale_b)
+    M, K = a.shape
+    N = b_kn.shape[1]
+    dt = norm_weight.dtype
+    assert norm_weight.is_contiguous() and norm_weight.numel() == N and (want_q or want_out)
+    if residual is not None:
+        assert residual.dtype == dt and residual.shape == (M, N) and residual.is_contiguous()
+    out = torch.empty(M, N, dtype=dt, device=a.device) if want_out else None
+    q = torch.empty(M, N, dtype=torch.int8, device=a.device) if want_q else None
+    scales = torch.empty(M, 1, dtype=torch.float32, device=a.device) if want_q else None
+    ws, nbytes = _int8_fused_ws(M, N, K, a.device)
+    check(lib.mi_int8_gemm_add_rmsnorm_int8(_ptr(a), _ptr(b_kn), _ptr(scale_a), _ptr(scale_b), _ptr(residual),
+                                            _ptr(norm_weight), _ptr(out), _ptr(q), _ptr(scales), M, N, K, a.stride(0),
+                                            b_kn.stride(1), float(eps), _DT[dt], _ptr(ws), nbytes, _stream()),
+          "mi_int8_gemm_add_rmsnorm_int8")
+    return out, q, scales
+
+
+def int8_gemm_rope_kvwrite(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                           positions: torch.Tensor, cos_sin_cache: torch.Tensor, k_cache: torch.Tensor,
+                           v_cache: torch.Tensor, loc: torch.Tensor, num_q_heads: int, num_kv_heads: int,
+                           head_dim: int) -> torch.Tensor:
+    """qkv int8 linear + NeoX RoPE + KV-pool write; returns q [M, Hq*D] in the pool dtype (bf16 / fp16 pools)."""
+    _check_int8_operands(a, b_kn, scale_a, scale_b)
+    M, K = a.shape
+    N = b_kn.shape[1]
+    assert N == (num_q_heads + 2 * num_kv_heads) * head_dim
+    assert positions.dtype == torch.int64 and loc.dtype == torch.int64 and positions.numel() == M and loc.numel() == M
+    assert cos_sin_cache.dtype == torch.float32 and cos_sin_cache.shape[1] == head_dim and cos_sin_cache.is_contiguous()
+    assert k_cache.dtype == v_cache.dtype and k_cache.dtype in _DT and k_cache[0].is_contiguous() and v_cache[0].is_contiguous()
+    assert k_cache[0].numel() == num_kv_heads * head_dim and v_cache[0].numel() == num_kv_heads * head_dim
+    q = torch.empty(M, num_q_heads * head_dim, dtype=k_cache.dtype, device=a.device)
+    ws, nbytes = _int8_fused_ws(M, N, K, a.device)
+    check(lib.mi_int8_gemm_rope_kvwrite(_ptr(a), _ptr(b_kn), _ptr(scale_a), _ptr(scale_b), _ptr(positions),
+                                        _ptr(cos_sin_cache), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(loc), M,
+                                        num_q_heads, num_kv_heads, head_dim, K, a.stride(0), b_kn.stride(1), q.stride(0),
+                                        k_cache.stride(0), v_cache.stride(0), _dt(k_cache), _ptr(ws), nbytes, _stream()),
+          "mi_int8_gemm_rope_kvwrite")
+    return q
+
+
+def int8_gemm_silu_mul(a: torch.Tensor, b_kn: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                       act_dtype: torch.dtype) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gate_up int8 linear + SiLU(gate)*up (rounded to act_dtype) + per-token int8 quant: (q int8 [M,I], scales [M,1])."""
+    _check_int8_operands(a, b_kn, scale_a, scale_b)
+    M, K = a.shape
+    N = b_kn.shape[1]
+    assert N % 2 == 0
+    q = torch.empty(M, N // 2, dtype=torch.int8, device=a.device)
+    scales = torch.empty(M, 1, dtype=torch.float32, device=a.device)
+    ws, nbytes = _int8_fused_ws(M, N, K, a.device)
+    check(lib.mi_int8_gemm_silu_mul_int8(_ptr(a), _ptr(b_kn), _ptr(scale_a), _ptr(scale_b), _ptr(q), _ptr(scales), M,
+                                         N // 2, K, a.stride(0), b_kn.stride(1), _DT[act_dtype], _ptr(ws), nbytes,
+                                         _stream()), "mi_int8_gemm_silu_mul_int8")
+    return q, scales
+
+
 # -------------------------------------------------------------------------- bf16 / fp16
 def _out_code(x: torch.Tensor, out_dtype: torch.dtype) -> int:
     assert out_dtype in (x.dtype, torch.float32), "out is the dtype of x or fp32"

@@ -77,3 +77,29 @@ class W8A8Int8LinearMethod(LinearMethodBase):
         xq, x_scale = ops.int8_quant_per_token(x2)
         out = ops.int8_gemm(xq, layer.weight, x_scale, layer.weight_scale, x.dtype, bias)
         return out.reshape(*x.shape[:-1], out.shape[-1])
+
+    def apply_prequantized(self, layer: torch.nn.Module, xq: torch.Tensor, x_scale: torch.Tensor,
+                           out_dtype: torch.dtype, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`apply` minus the activation quantisation: (xq, x_scale) come from a producer that already emitted int8
+        (ops.rmsnorm_int8 / silu_and_mul_int8 / a fused consumer)."""
+        return ops.int8_gemm(xq, layer.weight, x_scale, layer.weight_scale, out_dtype, bias)
+
+    # ---- decode batches: the linear fused with its consumer (mi_int8_gemm_* forms, M <= 256, no bias)
+    def fused_decode8_ok(self, layer: torch.nn.Module, M: int) -> bool:
+        K, N = layer.weight.shape
+        return getattr(layer, "bias", None) is None and ops.int8_fused_ok(M, N, K)
+
+    def apply_rope_kvwrite8(self, layer, xq, x_scale, positions, cos_sin_cache, k_cache, v_cache, loc, num_q_heads,
+                            num_kv_heads, head_dim):
+        """q = rope(linear(xq)[:, :q]); k (rope) and v rows go straight into the KV pool at `loc`."""
+        return ops.int8_gemm_rope_kvwrite(xq, layer.weight, x_scale, layer.weight_scale, positions, cos_sin_cache, k_cache,
+                                          v_cache, loc, num_q_heads, num_kv_heads, head_dim)
+
+    def apply_add_rmsnorm8(self, layer, xq, x_scale, residual, norm_weight, eps, want_q=True, want_out=False):
+        """(out | None, q | None, scales | None) of rmsnorm(linear(xq) + residual) * norm_weight; residual updated in place."""
+        return ops.int8_gemm_add_rmsnorm(xq, layer.weight, x_scale, layer.weight_scale, residual, norm_weight, eps,
+                                         want_q, want_out)
+
+    def apply_silu_mul8(self, layer, xq, x_scale, act_dtype):
+        """(q, scales) = per-token int8 of silu(gate) * up, linear(xq) = [gate | up]."""
+        return ops.int8_gemm_silu_mul(xq, layer.weight, x_scale, layer.weight_scale, act_dtype)

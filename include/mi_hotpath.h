@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 12
+#define MI_ABI_VERSION 13
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -406,6 +406,60 @@ int mi_int8_gemm(const void* a, const void* b_nk, const float* scale_a, const fl
 /* bytes of split-K scratch mi_int8_gemm can use for this shape (0: none needed); negative: the shape itself
  * (K % 64, K > 131072) is unsupported. */
 int64_t mi_int8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+
+/* Producers that hand the next W8A8 int8 linear its activation: mi_rmsnorm / mi_silu_and_mul followed by
+ * mi_int8_quant_per_token on the T-rounded result, in ONE launch and bit for bit.  q_out int8 [M,H] / [M,I] contiguous,
+ * q_scales fp32 [M] (the quant arithmetic documented above); `out` (T, nullable) is still written when given.
+ * One workgroup per row; rows up to 4096 wide stay in registers between the passes, wider ones are parked in LDS.
+ *   MI_ERR_UNSUPPORTED unless H % 8 == 0 (I % 8 == 0), every row stride % 8 == 0, H <= 16384, I <= 65536.
+ * replaces: RMSNorm.forward_native (layers/layernorm.py:128-146) / SiluAndMul.forward_native (layers/activation.py:56-58)
+ * followed by the per_token_quant_int8 of W8A8Int8LinearMethod.apply (quantization/w8a8_int8.py:136-145). */
+int mi_rmsnorm_int8(const void* x, void* residual /* nullable, in/out */, const void* weight, void* out /* nullable */,
+                    void* q_out, float* q_scales, int64_t M, int64_t H, int64_t ldx, int64_t ldr, int64_t ldo, float eps,
+                    int dtype, void* stream);
+int mi_silu_and_mul_int8(const void* x, void* out /* nullable */, void* q_out, float* q_scales, int64_t M, int64_t I,
+                         int64_t ldx, int64_t ldo, int dtype, void* stream);
+
+/* ------------------------- decode-shaped W8A8 int8 linears fused with their consumer
+ *
+ * M <= 256 (one pass of the int8 decode kernel), K % 64 == 0, N % 8 == 0, no bias, plus the alignment and 32-bit-offset
+ * rules of mi_int8_gemm.  The GEMM leaves raw int32 split-K partials in `workspace` (at least
+ * mi_int8_gemm_fused_workspace_bytes(M,N,K) bytes, 16-byte aligned; less is MI_ERR_INVALID; the query answers 0 where
+ * no fused form exists) and ONE consumer kernel sums them (exactly), applies mi_int8_gemm's epilogue
+ * x = round_T(((float)acc * scale_a[m]) * scale_b[n]) and the next op(s) of the decoder layer: two launches per call,
+ * no atomics, bit-identical to the unfused sequence of mi_int8_gemm and the kernels named below
+ * (tests/test_int8_fused_gpu.py).  scale_a fp32 [M], scale_b fp32 [N] (16-byte aligned). */
+int64_t mi_int8_gemm_fused_workspace_bytes(int64_t M, int64_t N, int64_t K);
+
+/* x = a.b_nk (o_proj / down_proj); x32 = x (+ residual, updated in place, nullable); y = rmsnorm(x32) * norm_weight
+ * -> out (T [M,N], nullable) and/or q_out int8 [M,N] + q_scales fp32 [M] = per-token int8 of y (nullable).  N <= 16384.
+ * replaces: int8_scaled_mm (quantization/w8a8_int8.py:136-145) + RMSNorm.forward_native with residual
+ * (layers/layernorm.py:128-146) + the per_token_quant_int8 of the next linear (w8a8_int8.py:136-145). */
+int mi_int8_gemm_add_rmsnorm_int8(const void* a, const void* b_nk, const float* scale_a, const float* scale_b,
+                                  void* residual, const void* norm_weight, void* out /* nullable */,
+                                  void* q_out /* nullable */, float* q_scales, int64_t M, int64_t N, int64_t K, int64_t lda,
+                                  int64_t ldb, float eps, int dtype, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
+/* qkv = a.b_nk with N = (Hq + 2*Hkv)*D; NeoX RoPE on q and k; q -> q_out [M, Hq*D] (row stride ldq);
+ * k -> k_cache[loc[t]], v -> v_cache[loc[t]] (slot strides in elements; T-typed pools only).  D % 16 == 0.
+ * replaces: int8_scaled_mm (quantization/w8a8_int8.py:136-145) + RotaryEmbedding.forward_native
+ * (layers/rotary_embedding.py:49-166) + MHATokenToKVPool.set_kv_buffer (mem_cache/memory_pool.py:454-455). */
+int mi_int8_gemm_rope_kvwrite(const void* a, const void* b_nk, const float* scale_a, const float* scale_b,
+                              const int64_t* positions, const float* cos_sin_cache, void* q_out, void* k_cache,
+                              void* v_cache, const int64_t* loc, int64_t M, int64_t num_q_heads, int64_t num_kv_heads,
+                              int64_t head_dim, int64_t K, int64_t lda, int64_t ldb, int64_t ldq, int64_t cache_stride_k,
+                              int64_t cache_stride_v, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* gate_up = a.b_nk with N = 2*I; q_out int8 [M,I], q_scales fp32 [M] = per-token int8 of round_T(silu(gate) * up).
+ * I % 64 == 0 (it is the next GEMM's K).  The per-token scale needs the whole row, so the activation cannot run in the
+ * GEMM's epilogue: when the GEMM's plan does not split K (N fills the chip) the ordinary kernel writes a T-typed
+ * [M, 2I] intermediate into `workspace` (half the bytes of an int32 slab), otherwise the slabs are consumed directly.
+ * replaces: int8_scaled_mm (quantization/w8a8_int8.py:136-145) + SiluAndMul.forward_native
+ * (layers/activation.py:56-58) + the per_token_quant_int8 of down_proj (w8a8_int8.py:136-145). */
+int mi_int8_gemm_silu_mul_int8(const void* a, const void* b_nk, const float* scale_a, const float* scale_b, void* q_out,
+                               float* q_scales, int64_t M, int64_t I, int64_t K, int64_t lda, int64_t ldb, int dtype,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* -------------------------------------------------------- int4 weight-only GEMM */
 
