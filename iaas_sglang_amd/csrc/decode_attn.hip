@@ -409,6 +409,272 @@ void decode_attn_kernel(const DecodeParams p) {
   });
 }
 
+// ---------------------------------------------------------------------------------------------
+// head_dim 256 (Gemma-class heads, 512-byte rows), bf16 / fp16 pool.  The organisation is that of decode_attn_kernel
+// (one wave per (request, kv head, split), W kv heads per workgroup, no LDS, no barriers, K rows straight from HBM into
+// the MFMA A fragment, deferred rescale, P.V on VALU with P broadcast by DPP); the V side and the ring are its own:
+//   V   a 512-byte row is two 256-byte halves.  Lane (row R, col c) still owns tokens 4R + i (the tokens whose P it can
+//       get by row_newbcast) and fetches TWO 16-byte pieces of each: dims 8c .. 8c+7 and 128 + 8c .. +7.  Every load
+//       instruction reads 4 tokens x 256 contiguous bytes, the pattern of the D = 128 kernel; accumulators acc[G][16]
+//       (j < 8: dims 8c + j, j >= 8: dims 128 + 8c + j - 8).
+//   K   8 k-steps: lane (row R, col c) holds dims 32 ks + 8R .. +7 of token c -- 16 lanes x 4 rows read whole 64-byte
+//       sectors of 16 rows per instruction, as before.
+//   ring  a tile is 32 (K) + 32 (V) VGPRs, and Q is another 32.  The K half and the V half of a ring slot are refilled
+//       SEPARATELY: K of tile n + NB is requested as soon as the score MFMAs of tile n have read the slot, V of tile
+//       n + NB after the P.V of tile n.  With NB = 1 (G = 4, 8: up to 128 accumulators + 64 + 32) half a tile to one tile (8-16
+//       KB) is still in flight per wave while it computes; G <= 2 keeps NB = 2 (16-32 KB in flight).
+//   The body is branch-free as in the fp8-pool form of decode_attn_kernel (tiles past the end are fully masked and
+//   their loads are clamped to the split's last row), so the refills go straight into the slot registers.
+template <typename T, int G, int W>
+__global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(2)))
+void decode_attn256_kernel(const DecodeParams p) {
+  constexpr int D = 256, KS = 8;
+  constexpr int NB = G <= 2 ? 2 : 1;     // 16 G + 64 NB + 32 (Q) <= 224: the rest of the 256 is addresses, scores, one converted V piece
+  typedef typename Elem<T>::vec8 vec8;
+
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int row = lane >> 4, col = lane & 15;
+  if (p.plan && (int)blockIdx.x >= p.plan[0]) return;
+  const int b = p.work ? p.work[2 * blockIdx.x] : (int)blockIdx.x;
+  const int hk = blockIdx.y * W + wave;
+  const int s = p.work ? p.work[2 * blockIdx.x + 1] : (int)blockIdx.z;
+  if (hk >= p.num_kv_heads) return;
+  const int group = p.group;
+  const int nsplit = p.num_splits;                       // workspace stride (the capacity when a plan is given)
+  const int nsplit_eff = p.plan ? p.plan[1] : nsplit;    // splits of this launch
+  const int32_t chunk_eff = p.plan ? p.plan[2] : p.split_chunk;
+
+  const int32_t base = p.kv_indptr[b];
+  const int32_t S = p.kv_indptr[b + 1] - base;
+  int32_t per = (S + nsplit_eff - 1) / nsplit_eff;       // the split rule of decode_attn_kernel (the merge relies on it)
+  per = (per + 15) & ~15;
+  per = max(per, chunk_eff);
+  const int32_t start = s * per;
+  const int32_t end = min(S, start + per);
+  const int hq0 = hk * group;
+
+  if (start >= end) {  // empty split (or empty request)
+    if (nsplit > 1) {
+      if (row == 0 && col < group) {
+        float* ml = p.ws_ml + (((int64_t)b * p.num_q_heads + hq0 + col) * nsplit + s) * 2;
+        ml[0] = -INFINITY;
+        ml[1] = 0.f;
+      }
+    } else if (row < 2) {   // lane (row h, col c): dims 128 h + 8 c .. + 7
+      for (int g = 0; g < group; ++g) {
+        T* o = (T*)p.o + (int64_t)b * p.stride_o_tok + (int64_t)(hq0 + g) * D + row * 128 + col * 8;
+        if (p.o) *(uint4*)o = make_uint4(0, 0, 0, 0);
+        if (p.o_q) *(uint2*)(p.o_q + ((int64_t)b * p.num_q_heads + hq0 + g) * D + row * 128 + col * 8) = make_uint2(0, 0);
+      }
+    }
+    return;
+  }
+
+  // ---- Q fragments (B operand): lane -> qhead col, dims 32*ks + 8*row .. +8
+  vec8 qf[KS];
+  {
+    const T* q = (const T*)p.q + (int64_t)b * p.stride_q_tok + (int64_t)(hq0 + col) * D + row * 8;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      uint4 z = make_uint4(0, 0, 0, 0);
+      if (col < group) z = *(const uint4*)(q + ks * 32);
+      qf[ks] = __builtin_bit_cast(vec8, z);
+    }
+  }
+
+  const int32_t* idx = p.kv_indices + (p.page_indptr ? p.page_indptr[b] : base);
+  const int32_t pshift = p.page_indptr ? p.page_shift : 0, pmask = (1 << pshift) - 1;
+  const T* kb = (const T*)p.k_buf + (int64_t)hk * D + row * 8;
+  const uint32_t kstride = (uint32_t)p.stride_k_slot, vstride = (uint32_t)p.stride_v_slot;   // < 2^31 (host check)
+  const T* vb = (const T*)p.v_buf + (int64_t)hk * D + col * 8;
+
+  float acc[G][16];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[g][j] = 0.f;
+  float m = -INFINITY, lsum = 0.f;
+
+  uint4 kf[NB][KS];      // K half of the ring: token col, dims 32 ks + 8 row
+  uint4 vv[NB][4][2];    // V half: token 4 row + i, dims 8 col (+ 128)
+
+  // kv_indices by 64-token blocks, two blocks ahead, handed out with ds_bpermute (see decode_attn_kernel)
+  auto load_idx_block = [&](int32_t blk) __attribute__((always_inline)) -> int32_t {
+    const int32_t t = min(start + blk * 64 + lane, end - 1);
+    return (idx[t >> pshift] << pshift) | (t & pmask);
+  };
+  auto load_k = [&](uint4 (&k)[KS], int32_t vblk, int j) __attribute__((always_inline)) {
+    const int32_t ik = __shfl(vblk, 16 * j + col);
+    const T* kp = kb + (uint64_t)(uint32_t)ik * kstride;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) k[ks] = ldg16<true>(kp + ks * 32);
+  };
+  auto load_v = [&](uint4 (&v)[4][2], int32_t vblk, int j) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int32_t iv = __shfl(vblk, 16 * j + 4 * row + i);
+      const T* vp = vb + (uint64_t)(uint32_t)iv * vstride;
+      v[i][0] = ldg16<true>(vp);
+      v[i][1] = ldg16<true>(vp + 128);
+    }
+  };
+
+  // scores of one tile -> probabilities pr[i] of tokens 4 row + i (C layout: lane col = q head); rescales acc / lsum
+  auto softmax = [&](f32x4 sacc, int32_t t0, float (&pr)[4]) __attribute__((always_inline)) {
+    float sc[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float x;
+      if (p.logit_cap > 0.f) {
+        float y = sacc[r] * p.sm_scale / p.logit_cap;
+        float e = __expf(2.f * y);
+        x = p.logit_cap * (1.f - 2.f / (e + 1.f)) * 1.4426950408889634f;
+      } else {
+        x = sacc[r] * p.scale_log2;
+      }
+      sc[r] = x;
+    }
+    if (t0 + 16 > end) {   // the last live tile and the masked ones behind it: a scalar branch
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sc[r] = (t0 + 4 * row + r < end) ? sc[r] : -INFINITY;
+    }
+    float tm = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
+    tm = fmaxf(tm, __shfl_xor(tm, 16));
+    tm = fmaxf(tm, __shfl_xor(tm, 32));
+    const bool grow = (col < group) && (tm > m + RESCALE_THR);
+    if (__any(grow)) {
+      const float mn = fmaxf(m, tm);
+      const float alpha = fast_exp2(m - mn);  // m = -inf on the first tile -> 0
+      m = mn;
+      lsum *= alpha;
+      static_for<0, G>([&](auto gi) {
+        constexpr int g = decltype(gi)::value;
+        const float a = row_bcast<g>(alpha);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[g][j] *= a;
+      });
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pr[r] = fast_exp2(sc[r] - m);
+      lsum += pr[r];
+    }
+  };
+  auto pv = [&](const uint4 (&v)[4][2], const float (&pr)[4]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const uint32_t w[4] = {v[i][h].x, v[i][h].y, v[i][h].z, v[i][h].w};
+        float vf[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          vf[2 * j] = Elem<T>::lo(w[j]);
+          vf[2 * j + 1] = Elem<T>::hi(w[j]);
+        }
+        static_for<0, G>([&](auto gi) {
+          constexpr int g = decltype(gi)::value;
+          const float pg = row_bcast<g>(pr[i]);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[g][8 * h + j] = fmaf(pg, vf[j], acc[g][8 * h + j]);
+          // Pin the sums here (no instruction).  The softmax of the next tile has branches, and the FMAs -- whose
+          // results nobody reads before the next rescale -- were otherwise SUNK past them, behind the next tile's
+          // MFMAs: the V half stayed live next to its own refill, every P broadcast was kept, and all instances
+          // spilled (G = 8: 736 B per lane).
+          float* a = &acc[g][8 * h];
+          asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
+        });
+        // one 16-byte piece at a time: left alone, the scheduler converts all 64 V values of the tile up front
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  };
+
+  const int32_t ntiles = (end - start + 15) >> 4;
+  int32_t vcur = load_idx_block(0);
+  int32_t vnext = load_idx_block(1);
+  static_for<0, NB>([&](auto ji) {
+    constexpr int j = decltype(ji)::value;
+    load_k(kf[j], vcur, j);
+    load_v(vv[j], vcur, j);
+  });
+  for (int32_t tb = 0; tb < ntiles; tb += 4) {   // one 64-token index block per iteration
+    const int32_t vafter = load_idx_block((tb >> 2) + 2);
+    static_for<0, 4>([&](auto ji) {
+      constexpr int j = decltype(ji)::value;
+      constexpr int slot = j % NB;
+      f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) sacc = Elem<T>::mfma16(__builtin_bit_cast(vec8, kf[slot][ks]), qf[ks], sacc);
+      float pr[4];
+      softmax(sacc, start + (tb + j) * 16, pr);
+      // the K half is free: refill it before the P.V of this tile.  (The barrier sits behind the softmax, not between
+      // the MFMA chain and the first read of its result: see the note on sched_barrier next to MFMAs in extend_attn.hip.)
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (j + NB < 4) load_k(kf[slot], vcur, j + NB);
+      else load_k(kf[slot], vnext, j + NB - 4);
+      pv(vv[slot], pr);
+      __builtin_amdgcn_sched_barrier(0);   // and the V half after it
+      if constexpr (j + NB < 4) load_v(vv[slot], vcur, j + NB);
+      else load_v(vv[slot], vnext, j + NB - 4);
+    });
+    vcur = vnext;
+    vnext = vafter;
+  }
+
+  // ---- combine the partial sums held by the 4 lane rows
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      float x = acc[g][j];
+      x += __shfl_xor(x, 16);
+      x += __shfl_xor(x, 32);
+      acc[g][j] = x;
+    }
+  lsum += __shfl_xor(lsum, 16);
+  lsum += __shfl_xor(lsum, 32);
+
+  static_for<0, G>([&](auto gi) {
+    constexpr int g = decltype(gi)::value;
+    const float lg = row_bcast<g>(lsum);
+    const float mg = row_bcast<g>(m);
+    if (g < group && row < 2) {    // lane rows 0 / 1 write the halves dims 8 col .. and 128 + 8 col ..
+      const int64_t hq = hq0 + g;
+      float a[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] = row ? acc[g][8 + j] : acc[g][j];
+      const int d0 = row * 128 + col * 8;
+      if (nsplit == 1) {
+        const float inv = 1.f / lg;
+        uint4 out;
+        out.x = pack2<T>(a[0] * inv, a[1] * inv);
+        out.y = pack2<T>(a[2] * inv, a[3] * inv);
+        out.z = pack2<T>(a[4] * inv, a[5] * inv);
+        out.w = pack2<T>(a[6] * inv, a[7] * inv);
+        if (p.o) *(uint4*)((T*)p.o + (int64_t)b * p.stride_o_tok + hq * D + d0) = out;
+        if (p.o_q) {
+          const float qs = *p.o_qscale;
+          const float qinv = qs > 0.f ? 1.0f / qs : 0.f;
+          uint2 w;
+          w.x = quant4_static<T>(a[0] * inv, a[1] * inv, a[2] * inv, a[3] * inv, qinv);
+          w.y = quant4_static<T>(a[4] * inv, a[5] * inv, a[6] * inv, a[7] * inv, qinv);
+          *(uint2*)(p.o_q + ((int64_t)b * p.num_q_heads + hq) * D + d0) = w;
+        }
+      } else {
+        const int64_t slot = ((int64_t)b * p.num_q_heads + hq) * nsplit + s;
+        float4* wo = (float4*)(p.ws_o + slot * D + d0);
+        wo[0] = make_float4(a[0], a[1], a[2], a[3]);
+        wo[1] = make_float4(a[4], a[5], a[6], a[7]);
+        if (lane == 0) {
+          p.ws_ml[slot * 2] = mg;
+          p.ws_ml[slot * 2 + 1] = lg;
+        }
+      }
+    }
+  });
+}
+
 // ---- stage 2: merge the per-split partials (one wave per (b, qhead)) -------------------
 template <typename T, int D>
 __global__ __launch_bounds__(256) void decode_merge_kernel(const float* __restrict__ ws_o,
@@ -486,7 +752,9 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(const float* __restri
       const float qs = *o_qscale;
       const float qinv = qs > 0.f ? 1.0f / qs : 0.f;
       uint8_t* out = o_q + bh * D + lane * EPL;
-      if constexpr (EPL == 2) {
+      if constexpr (EPL == 4) {
+        *(uint32_t*)out = quant4_static<T>(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv, qinv);
+      } else if constexpr (EPL == 2) {
         const uint32_t w = quant4_static<T>(acc[0] * inv, acc[1] * inv, 0.f, 0.f, qinv);
         *(uint16_t*)out = (uint16_t)(w & 0xffffu);
       } else {
@@ -504,8 +772,8 @@ MI_INTERNAL int mi_attn_merge_splits(const float* ws_o, const float* ws_ml, void
   const unsigned blocks = (unsigned)cdiv64(n_bh, 4);
   hipStream_t st = (hipStream_t)stream;
 #define MERGE_X(TT, DD) decode_merge_kernel<TT, DD><<<blocks, 256, 0, st>>>(ws_o, ws_ml, (TT*)o, n_bh, (int)num_q_heads, (int)num_splits, stride_o_tok, nullptr, nullptr, 1.f, nullptr, 0, nullptr)
-  if (dtype == MI_BF16) { if (head_dim == 128) MERGE_X(bf16_t, 128); else MERGE_X(bf16_t, 64); }
-  else { if (head_dim == 128) MERGE_X(f16_t, 128); else MERGE_X(f16_t, 64); }
+  if (dtype == MI_BF16) { if (head_dim == 256) MERGE_X(bf16_t, 256); else if (head_dim == 128) MERGE_X(bf16_t, 128); else MERGE_X(bf16_t, 64); }
+  else { if (head_dim == 256) MERGE_X(f16_t, 256); else if (head_dim == 128) MERGE_X(f16_t, 128); else MERGE_X(f16_t, 64); }
 #undef MERGE_X
   MI_CHECK_LAUNCH();
   return MI_OK;
@@ -542,6 +810,31 @@ static void launch_decode_w(const DecodeParams& p, int64_t batch, hipStream_t st
   else launch_decode<T, D, G, 1, KV8>(p, batch, st);
 }
 
+// head_dim 256: W as for the other widths (8 kv heads per workgroup = one 4-KB slot of an 8-head pool per token)
+template <typename T, int G>
+static void launch_decode256_w(const DecodeParams& p, int64_t batch, hipStream_t st) {
+  const int h = p.num_kv_heads;
+  int w = h % 8 == 0 ? 8 : h % 4 == 0 ? 4 : h % 2 == 0 ? 2 : 1;
+  const int64_t items = p.work ? p.num_work : batch * p.num_splits;
+  while (w > 2 && items * (h / w) < 256) w >>= 1;
+  dim3 grid((unsigned)(p.work ? p.num_work : batch), (unsigned)(h / w), (unsigned)(p.work ? 1 : p.num_splits));
+  if (w == 8) decode_attn256_kernel<T, G, 8><<<grid, 512, 0, st>>>(p);
+  else if (w == 4) decode_attn256_kernel<T, G, 4><<<grid, 256, 0, st>>>(p);
+  else if (w == 2) decode_attn256_kernel<T, G, 2><<<grid, 128, 0, st>>>(p);
+  else decode_attn256_kernel<T, G, 1><<<grid, 64, 0, st>>>(p);
+}
+
+template <typename T>
+static int launch_decode256_g(const DecodeParams& p, int64_t batch, hipStream_t st) {
+  const int g = p.group;
+  if (g == 1) launch_decode256_w<T, 1>(p, batch, st);
+  else if (g == 2) launch_decode256_w<T, 2>(p, batch, st);
+  else if (g <= 4) launch_decode256_w<T, 4>(p, batch, st);
+  else if (g <= 8) launch_decode256_w<T, 8>(p, batch, st);
+  else return MI_ERR_UNSUPPORTED;      // 16 q heads x 16 accumulators = the whole register file
+  return MI_OK;
+}
+
 template <typename T, int D, bool KV8 = false>
 static int launch_decode_g(const DecodeParams& p, int64_t batch, hipStream_t st) {
   const int g = p.group;
@@ -572,8 +865,11 @@ static int decode_attn_impl(const void* q, const void* k_buf, const void* v_buf,
   MI_CHECK_ARG(num_splits == 1 || workspace != nullptr);
   MI_CHECK_ARG(split_chunk >= 0 && split_chunk % 16 == 0 && split_chunk < (1 << 30));
   MI_CHECK_ARG(dtype == MI_BF16 || dtype == MI_FP16);
-  if (head_dim != 64 && head_dim != 128)
-    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_decode_attn: head_dim %lld not supported (64, 128)", (long long)head_dim);
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256)
+    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_decode_attn: head_dim %lld not supported (64, 128, 256)", (long long)head_dim);
+  if (head_dim == 256 && num_q_heads / num_kv_heads > 8)
+    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_decode_attn: group size %lld not supported at head_dim 256 (<= 8)",
+            (long long)(num_q_heads / num_kv_heads));
   if (kv8 && head_dim != 128) MI_FAIL(MI_ERR_UNSUPPORTED, "mi_decode_attn_fp8kv: head_dim 128 only");
   MI_CHECK_ARG(k_scale > 0.f && v_scale > 0.f);
   MI_CHECK_ARG(!kv8 || (stride_k_slot % 16 == 0 && stride_v_slot % 16 == 0));
@@ -612,6 +908,8 @@ static int decode_attn_impl(const void* q, const void* k_buf, const void* v_buf,
   int rc;
   if (kv8)
     rc = dtype == MI_BF16 ? launch_decode_g<bf16_t, 128, true>(p, batch, st) : launch_decode_g<f16_t, 128, true>(p, batch, st);
+  else if (head_dim == 256)
+    rc = dtype == MI_BF16 ? launch_decode256_g<bf16_t>(p, batch, st) : launch_decode256_g<f16_t>(p, batch, st);
   else if (dtype == MI_BF16)
     rc = head_dim == 128 ? launch_decode_g<bf16_t, 128>(p, batch, st) : launch_decode_g<bf16_t, 64>(p, batch, st);
   else
@@ -625,7 +923,12 @@ static int decode_attn_impl(const void* q, const void* k_buf, const void* v_buf,
     // without a work list every (request, split) workgroup ran and wrote its (m, l) -- empty splits l = 0 -- so the
     // merge need not derive the live splits from kv_indptr (a dependent load in front of its first read)
     if (!p.work) kv_indptr = nullptr;
-    if (dtype == MI_BF16) {
+    if (head_dim == 256) {
+      if (dtype == MI_BF16)
+        decode_merge_kernel<bf16_t, 256><<<blocks, 256, 0, st>>>(p.ws_o, p.ws_ml, (bf16_t*)o, n_bh, p.num_q_heads, p.num_splits, stride_o_tok, p.o_q, p.o_qscale, p.v_scale, kv_indptr, p.split_chunk, p.plan);
+      else
+        decode_merge_kernel<f16_t, 256><<<blocks, 256, 0, st>>>(p.ws_o, p.ws_ml, (f16_t*)o, n_bh, p.num_q_heads, p.num_splits, stride_o_tok, p.o_q, p.o_qscale, p.v_scale, kv_indptr, p.split_chunk, p.plan);
+    } else if (dtype == MI_BF16) {
       if (head_dim == 128)
         decode_merge_kernel<bf16_t, 128><<<blocks, 256, 0, st>>>(p.ws_o, p.ws_ml, (bf16_t*)o, n_bh, p.num_q_heads, p.num_splits, stride_o_tok, p.o_q, p.o_qscale, p.v_scale, kv_indptr, p.split_chunk, p.plan);
       else

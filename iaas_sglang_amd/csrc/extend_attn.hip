@@ -92,7 +92,11 @@ template <typename T> __device__ __forceinline__ uint4 fp8x8_to_T(uint2 u) {
 // KV8: the POOL (cached prefix) holds fp8 e4m3fn rows (strides in bytes); they are converted to T while being
 // staged (exact), k_scale multiplies the prefix logits and v_scale the prefix probabilities fed to the PV MFMA
 // (never the softmax denominator).  The new tokens (k_ext / v_ext) stay T-typed and unscaled.
-template <typename T, int D, int HG, int RT, int KH, bool KV8>  // HG q heads per workgroup (1, 2 or 4)
+// PSPLIT (head_dim 256, bf16, extends of <= 16 tokens): P goes into the PV MFMA as bf16 hi + bf16 lo (two MFMAs per V^T
+// fragment), i.e. with ~2^-17 relative error instead of bf16's 2^-9.  A one-token extend (chunk tail, verify step) then
+// agrees with the decode kernel -- which keeps P in fp32 -- to within the output rounding; these launches are bound by
+// the prefix gather, the MFMA pipe is idle.  fp16 P (2^-11) needs no split.
+template <typename T, int D, int HG, int RT, int KH, bool KV8, bool PSPLIT = false>  // HG q heads per workgroup (1, 2 or 4)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))   // <= 256 registers: two workgroups per CU
 void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
   constexpr int KS = D / 32;
@@ -160,9 +164,9 @@ void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
   // sub-tile of compute (the other LDS stage is free for the whole iteration), so only 32 keys' worth of
   // staging registers is live.  Named registers + macros: register ARRAYS here ended up in scratch.
   constexpr int NSUB = KH / 2;          // 32-key sub-tiles per LDS tile
-  constexpr int SPASS = 32 / TPR;       // staging passes per sub-tile (2 for D=128, 1 for D=64)
-  static_assert(SPASS == 1 || SPASS == 2, "staging passes");
-  uint4 kreg0, vreg0, kreg1, vreg1;
+  constexpr int SPASS = 32 / TPR;       // staging passes per sub-tile (4 for D=256, 2 for D=128, 1 for D=64)
+  static_assert(SPASS == 1 || SPASS == 2 || SPASS == 4, "staging passes");
+  uint4 kreg0, vreg0, kreg1, vreg1, kreg2, vreg2, kreg3, vreg3;
 #define STAGE_LOAD_ONE(tile_, sub_, ps_, KR, VR)                                                                \
   {                                                                                                             \
     int32_t kp_ = (tile_) * KT + (sub_) * 32 + srow + TPR * (ps_);                                              \
@@ -185,7 +189,11 @@ void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
 #define STAGE_LOAD(tile_, sub_)                                                  \
   {                                                                              \
     STAGE_LOAD_ONE(tile_, sub_, 0, kreg0, vreg0);                                \
-    if constexpr (SPASS == 2) STAGE_LOAD_ONE(tile_, sub_, 1, kreg1, vreg1);      \
+    if constexpr (SPASS >= 2) STAGE_LOAD_ONE(tile_, sub_, 1, kreg1, vreg1);      \
+    if constexpr (SPASS == 4) {                                                  \
+      STAGE_LOAD_ONE(tile_, sub_, 2, kreg2, vreg2);                              \
+      STAGE_LOAD_ONE(tile_, sub_, 3, kreg3, vreg3);                              \
+    }                                                                            \
   }
 #define STAGE_WRITE(st_, sub_)                                                               \
   {                                                                                          \
@@ -193,9 +201,15 @@ void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
     char* vsw_ = ksw_ + KT * ROW;                                                            \
     *(uint4*)ksw_ = kreg0;                                                                   \
     *(uint4*)vsw_ = vreg0;                                                                   \
-    if constexpr (SPASS == 2) {                                                              \
+    if constexpr (SPASS >= 2) {                                                              \
       *(uint4*)(ksw_ + TPR * ROW) = kreg1;                                                   \
       *(uint4*)(vsw_ + TPR * ROW) = vreg1;                                                   \
+    }                                                                                        \
+    if constexpr (SPASS == 4) {                                                              \
+      *(uint4*)(ksw_ + 2 * TPR * ROW) = kreg2;                                               \
+      *(uint4*)(vsw_ + 2 * TPR * ROW) = vreg2;                                               \
+      *(uint4*)(ksw_ + 3 * TPR * ROW) = kreg3;                                               \
+      *(uint4*)(vsw_ + 3 * TPR * ROW) = vreg3;                                               \
     }                                                                                        \
   }
 
@@ -248,6 +262,7 @@ void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
         // ---- scale, cap, mask, online softmax; P^T packed as the B operand of the PV MFMAs:
         // k-slot (g4, j): j<4 -> key 4*g4+j of the first half, j>=4 -> of the second
         vec8 pf[RT];
+        vec8 pf_lo[RT];   // PSPLIT only
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
           float sc[2][4];
@@ -321,6 +336,16 @@ void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
           const u32x4 pw = {pack2<T>(pr[0][0], pr[0][1]), pack2<T>(pr[0][2], pr[0][3]),
                             pack2<T>(pr[1][0], pr[1][1]), pack2<T>(pr[1][2], pr[1][3])};
           pf[rt] = __builtin_bit_cast(vec8, pw);
+          if constexpr (PSPLIT) {   // lo = P - (T)P, exact in fp32, then rounded to T
+            const uint32_t w[4] = {pw[0], pw[1], pw[2], pw[3]};
+            uint32_t l[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int h = j >> 1, r = 2 * (j & 1);
+              l[j] = pack2<T>(pr[h][r] - Elem<T>::lo(w[j]), pr[h][r + 1] - Elem<T>::hi(w[j]));
+            }
+            pf_lo[rt] = __builtin_bit_cast(vec8, u32x4{l[0], l[1], l[2], l[3]});
+          }
         }
         // ---- O^T += V^T . P^T ; V^T fragments by transposed LDS reads, each feeds the RT row tiles
         const int qq = c16 >> 2, pp = c16 & 3;
@@ -332,7 +357,10 @@ void extend_attn_kernel(const ExtendParams p, int nqb, int gy) {
           typedef __attribute__((ext_vector_type(8))) short s16x8;
           const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
-          for (int rt = 0; rt < RT; ++rt) acc[rt][db] = Elem<T>::mfma16(__builtin_bit_cast(vec8, both), pf[rt], acc[rt][db]);
+          for (int rt = 0; rt < RT; ++rt) {
+            acc[rt][db] = Elem<T>::mfma16(__builtin_bit_cast(vec8, both), pf[rt], acc[rt][db]);
+            if constexpr (PSPLIT) acc[rt][db] = Elem<T>::mfma16(__builtin_bit_cast(vec8, both), pf_lo[rt], acc[rt][db]);
+          }
         }
       }
       // the other stage was last read in the previous iteration (every wave is past that iteration's barrier)
@@ -858,14 +886,28 @@ static void launch_extend(const ExtendParams& p, int64_t batch, int64_t max_exte
   static const int big = mi_tune("MI_EXTEND_BIG", 0);
   const int gy = (int)(p.num_kv_heads * (p.group / HG));
   const int64_t gz = batch * p.num_splits;
-  if (big && max_extend_len > 16) {       // 128 rows x 64-key tiles, double-buffered
+  // head_dim 256 (512-byte rows): always the <1, 2> form -- 64 query rows x 32-key tiles.  One 16-row tile per wave
+  // keeps acc at 64 VGPRs and Q at 32; the 32-key tile is 2 stages x (K + V) x 32 rows x 544 B = 69,632 B of LDS, two
+  // workgroups per CU (<2, 4> would need 139 KB and 192 VGPRs of acc + Q); a 32-key sub-tile is staged in four
+  // 8-row passes (256 threads x 16 B = 8 rows of 512 B).  Row pitch 544 B = 136 dwords = 8 (mod 64 banks), the same
+  // residue as the 288-byte pitch of head_dim 128 (72 = 8 mod 64), and the d offsets added inside a row are the same
+  // for every lane of a read: +32 B stays conflict-free for the ds_read_b128 rows and the ds_read_b64_tr_b16 blocks.
+  if (D == 256 || !(big && max_extend_len > 16)) {
+    constexpr int BQ = 64 / HG;
+    const int64_t nqb = cdiv64(max_extend_len, BQ);
+    if constexpr (D == 256 && __is_same(T, bf16_t) && !KV8) {
+      if (max_extend_len <= 16) {
+        extend_attn_kernel<T, D, HG, 1, 2, KV8, true><<<(unsigned)(nqb * gy * gz), 256, 2 * 2 * 32 * ROW, st>>>(p, (int)nqb, gy);
+        return;
+      }
+    }
+    extend_attn_kernel<T, D, HG, 1, 2, KV8><<<(unsigned)(nqb * gy * gz), 256, 2 * 2 * 32 * ROW, st>>>(p, (int)nqb, gy);
+    return;
+  }
+  if constexpr (D != 256) {               // 128 rows x 64-key tiles, double-buffered
     constexpr int BQ = 128 / HG;
     const int64_t nqb = cdiv64(max_extend_len, BQ);
     extend_attn_kernel<T, D, HG, 2, 4, KV8><<<(unsigned)(nqb * gy * gz), 256, 2 * 2 * 64 * ROW, st>>>(p, (int)nqb, gy);
-  } else {                                // short extends (speculative verify, chunk tails): 64 rows x 32-key tiles
-    constexpr int BQ = 64 / HG;
-    const int64_t nqb = cdiv64(max_extend_len, BQ);
-    extend_attn_kernel<T, D, HG, 1, 2, KV8><<<(unsigned)(nqb * gy * gz), 256, 2 * 2 * 32 * ROW, st>>>(p, (int)nqb, gy);
   }
 }
 
@@ -942,8 +984,8 @@ static int extend_attn_impl(const void* q_ext, const void* k_ext, const void* v_
   MI_CHECK_ARG(cdiv64(max_extend_len, 16) * num_q_heads * batch * num_splits < (1ll << 31));
   MI_CHECK_ARG(num_splits == 1 || (workspace && total_tokens > 0 && ((uintptr_t)workspace & 15) == 0));
   MI_CHECK_ARG(dtype == MI_BF16 || dtype == MI_FP16);
-  if (head_dim != 64 && head_dim != 128)
-    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_extend_attn: head_dim %lld not supported (64, 128)", (long long)head_dim);
+  if (head_dim != 64 && head_dim != 128 && head_dim != 256)
+    MI_FAIL(MI_ERR_UNSUPPORTED, "mi_extend_attn: head_dim %lld not supported (64, 128, 256)", (long long)head_dim);
   MI_CHECK_ARG(stride_q_tok % 8 == 0 && stride_o_tok % 4 == 0 && stride_kx_tok % 8 == 0 &&
                stride_vx_tok % 8 == 0 && stride_k_slot % 8 == 0 && stride_v_slot % 8 == 0);
   MI_CHECK_ARG((((uintptr_t)q_ext | (uintptr_t)k_ext | (uintptr_t)v_ext | (uintptr_t)k_buf | (uintptr_t)v_buf) & 15) == 0);
@@ -986,10 +1028,12 @@ static int extend_attn_impl(const void* q_ext, const void* k_ext, const void* v_
     if (dtype == MI_BF16) launch_extend_g<bf16_t, 128, true>(p, batch, max_extend_len, st);
     else launch_extend_g<f16_t, 128, true>(p, batch, max_extend_len, st);
   } else if (dtype == MI_BF16) {
-    if (head_dim == 128) launch_extend_g<bf16_t, 128>(p, batch, max_extend_len, st);
+    if (head_dim == 256) launch_extend_g<bf16_t, 256>(p, batch, max_extend_len, st);
+    else if (head_dim == 128) launch_extend_g<bf16_t, 128>(p, batch, max_extend_len, st);
     else launch_extend_g<bf16_t, 64>(p, batch, max_extend_len, st);
   } else {
-    if (head_dim == 128) launch_extend_g<f16_t, 128>(p, batch, max_extend_len, st);
+    if (head_dim == 256) launch_extend_g<f16_t, 256>(p, batch, max_extend_len, st);
+    else if (head_dim == 128) launch_extend_g<f16_t, 128>(p, batch, max_extend_len, st);
     else launch_extend_g<f16_t, 64>(p, batch, max_extend_len, st);
   }
   MI_CHECK_LAUNCH();

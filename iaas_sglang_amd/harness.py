@@ -41,6 +41,7 @@ class ModelShape:
 LLAMA3_8B = ModelShape("Llama-3-8B", 4096, 32, 32, 8, 128, 14336, 128256)
 LLAMA2_7B = ModelShape("Llama-2-7B", 4096, 32, 32, 32, 128, 11008, 32000, rope_theta=10000.0, context_len=4096)
 LLAMA3_70B = ModelShape("Llama-3-70B", 8192, 80, 64, 8, 128, 28672, 128256)
+GEMMA2_9B = ModelShape("Gemma-2-9B", 3584, 42, 16, 8, 256, 14336, 256000, rms_eps=1e-6, rope_theta=10000.0)
 TINY = ModelShape("tiny-llama", 256, 2, 8, 2, 64, 512, 1000, context_len=512)
 
 

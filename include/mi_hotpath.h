@@ -129,6 +129,7 @@ int64_t mi_decode_attn_workspace_bytes(int64_t batch, int64_t num_q_heads, int64
  *   o [B,Hq,D] ; kv_indptr int32 [B+1] ; kv_indices int32 [kv_indptr[B]]
  *   o[b,h] = softmax_j(sm_scale * q[b,h].k_buf[kv_indices[kv_indptr[b]+j], h/group]) . v_buf[...]
  *   logit_cap > 0 applies cap*tanh(x/cap) to the scaled logits.
+ *   head_dim 64, 128 or 256 (256: bf16 / fp16 pool only, at most 8 q heads per kv head; else MI_ERR_UNSUPPORTED).
  *   num_splits >= 1; workspace needed when num_splits > 1.  split_chunk (multiple of 16, 0 = off): every split
  *   covers split_chunk keys -- balanced workgroups on RAGGED batches, short requests leave trailing splits empty;
  *   a request longer than num_splits * split_chunk falls back to ceil(S / num_splits) keys per split.
@@ -196,6 +197,8 @@ int mi_decode_attn_fp8kv(const void* q, const void* k_buf, const void* v_buf, vo
  *   into k_buf/v_buf.  Row j of request i attends the whole prefix plus new tokens 0..j
  *   (causal) or all new tokens (non-causal).  sliding_window > 0 additionally requires
  *   q_pos <= k_pos + sliding_window.
+ *   head_dim 64, 128 or 256 (256: bf16 / fp16 pool only, the general kernel in its 64-row x 32-key form; the
+ *   long-extend kernel and its fused forms stay head_dim 128).
  * replaces: extend_attention_fwd, triton_ops/extend_attention.py:306-438;
  * oracle: TorchNativeAttnBackend._run_sdpa_forward_extend, torch_native_backend.py:27-110. */
 int mi_extend_attn(const void* q_ext, const void* k_ext, const void* v_ext, void* o_ext,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of mi_decode_attn at the BASELINE shape (B=128, S=2048, Hq=32, Hkv=8, D=128).
+"""Micro-benchmark of mi_decode_attn at the BASELINE shape (B=128, S=2048, Hq=32, Hkv=8, D=128; env B, S, HQ, HKV, D).
 Cycles over several layer-sized pools so the 256 MB Infinity Cache cannot help.  Not a test."""
 import math
 import os
@@ -11,7 +11,7 @@ from iaas_sglang_amd import ops  # noqa: E402
 
 dev = "cuda"
 B = int(os.environ.get("B", "128")); S = int(os.environ.get("S", "2048"))
-Hq, Hkv, D = int(os.environ.get("HQ", "32")), int(os.environ.get("HKV", "8")), 128
+Hq, Hkv, D = int(os.environ.get("HQ", "32")), int(os.environ.get("HKV", "8")), int(os.environ.get("D", "128"))
 npool = int(os.environ.get("NPOOL", "6"))
 contig = os.environ.get("CONTIG", "0") == "1"
 slots = B * S + 1
@@ -106,5 +106,5 @@ for ns in [int(x) for x in os.environ.get("SPLITS", "1,2,4,8").split(",")]:
             run(k, v, ns, ws)
     e1.record(); e1.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / (reps * npool)
-    print(f"B={B} S={S} Hq={Hq} Hkv={Hkv} contig={int(contig)} page={PAGE} paged_kernel={os.environ.get('PAGED_KERNEL', '1') if PAGE > 1 else '-'} splits={ns} W={os.environ.get('MI_DECODE_W','auto')}: "
+    print(f"B={B} S={S} Hq={Hq} Hkv={Hkv} D={D} contig={int(contig)} page={PAGE} paged_kernel={os.environ.get('PAGED_KERNEL', '1') if PAGE > 1 else '-'} splits={ns} W={os.environ.get('MI_DECODE_W','auto')}: "
           f"{us:8.1f} us  {abytes/us/1e3:7.1f} GB/s", flush=True)
