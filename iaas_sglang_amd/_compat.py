@@ -8,6 +8,7 @@ method signatures are used -- they carry no arithmetic.  Citations: /root/refere
 from __future__ import annotations
 
 from abc import ABC, abstractmethod
+from dataclasses import dataclass
 from enum import IntEnum, auto
 from typing import Any, Dict, List, Optional
 
@@ -354,3 +355,44 @@ except Exception:  # ImportError or any of SGLang's own import-time failures
             if self.marlin_tile_size is not None:
                 return size * self.marlin_tile_size, offset * self.marlin_tile_size
             return size, offset
+
+try:  # pragma: no cover - exercised only inside an SGLang install
+    from sglang.srt.lora.backend.base_backend import BaseLoRABackend
+    from sglang.srt.lora.utils import LoRABatchInfo
+except Exception:
+
+    @dataclass
+    class LoRABatchInfo:
+        """python/sglang/srt/lora/utils.py:11-32."""
+        bs: int
+        seg_lens: torch.Tensor          # (bs,)
+        seg_indptr: torch.Tensor        # (bs + 1,)
+        max_len: int
+        weight_indices: torch.Tensor    # (bs,) adapter of each sequence
+        lora_ranks: torch.Tensor        # (lora_num,)
+        scalings: torch.Tensor          # (lora_num,)
+
+    class BaseLoRABackend:
+        """python/sglang/srt/lora/backend/base_backend.py:24-117 (its name table, :8-21, knows "triton" only)."""
+
+        def __init__(self, name: str, batch_info: LoRABatchInfo = None):
+            self.name = name
+            self.batch_info = batch_info
+            self.fuse_output_add = name == "triton"
+            self.fuse_stacked_lora_b = name == "triton"
+
+        def run_lora_a_sgemm(self, x: torch.Tensor, weights: torch.Tensor, *args, **kwargs) -> torch.Tensor:
+            pass
+
+        def run_lora_b_sgemm(self, x: torch.Tensor, weights: torch.Tensor, *args, **kwargs) -> torch.Tensor:
+            pass
+
+        def run_qkv_lora(self, x: torch.Tensor, qkv_lora_a: torch.Tensor, qkv_lora_b, *args, **kwargs) -> torch.Tensor:
+            pass
+
+        def run_gate_up_lora(self, x: torch.Tensor, gate_up_lora_a: torch.Tensor, gate_up_lora_b, *args,
+                             **kwargs) -> torch.Tensor:
+            pass
+
+        def set_batch_info(self, batch_info: LoRABatchInfo):
+            self.batch_info = batch_info

@@ -749,6 +749,55 @@ def bf16_gemm_tile(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     return out
 
 
+# -------------------------------------------------------------------- multi-LoRA
+def _lora_batch_args(seg_indptr: torch.Tensor, weight_indices: torch.Tensor, lora_ranks: torch.Tensor, bs: int):
+    assert seg_indptr.dtype == torch.int32 and seg_indptr.is_contiguous() and seg_indptr.numel() >= bs + 1
+    assert weight_indices.dtype == torch.int32 and weight_indices.is_contiguous() and weight_indices.numel() >= bs
+    assert lora_ranks.dtype in (torch.int32, torch.int64) and lora_ranks.is_contiguous()
+    return _ptr(seg_indptr), _ptr(weight_indices), _ptr(lora_ranks), int(lora_ranks.dtype == torch.int64)
+
+
+def lora_shrink(x: torch.Tensor, weights: torch.Tensor, seg_indptr: torch.Tensor, weight_indices: torch.Tensor,
+                lora_ranks: torch.Tensor, bs: int, max_len: int, stack_num: int = 1,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Segmented x [S,K] . weights[adapter] [N,K]^T -> out [S,N], N = stack_num * r_max.  Segment b (rows
+    seg_indptr[b] .. seg_indptr[b+1]) uses adapter weight_indices[b]; only its first stack_num * rank columns are
+    written (a fresh `out` is torch.empty, as the reference's).  x and out may be row-strided."""
+    (S, K), (num_lora, N, K2) = x.shape, weights.shape
+    assert K == K2 and x.dtype == weights.dtype and lora_ranks.numel() >= num_lora
+    assert x.stride(1) == 1 and weights.is_contiguous(), "rows of x are contiguous, weights is contiguous"
+    if out is None:
+        out = torch.empty(S, N, dtype=x.dtype, device=x.device)
+    assert out.shape == (S, N) and out.dtype == x.dtype and out.stride(1) == 1
+    check(lib.mi_lora_shrink(_ptr(x), _ptr(weights), _ptr(out), *_lora_batch_args(seg_indptr, weight_indices, lora_ranks, bs),
+                             S, N, K, stack_num, num_lora, x.stride(0), out.stride(0), bs, max_len, _dt(x), _stream()),
+          "mi_lora_shrink")
+    return out
+
+
+def lora_expand(x: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, seg_indptr: torch.Tensor,
+                weight_indices: torch.Tensor, lora_ranks: torch.Tensor, scalings: torch.Tensor, bs: int, max_len: int,
+                num_slices: int = 1, slice_width: Optional[int] = None,
+                n_offs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [S,N_out] += scalings[adapter] * (x [S, num_slices*R] . weights[adapter] [N_out,R]^T), slice by slice, in
+    place.  Slice j covers the output columns n_offs[j] .. n_offs[j+1] (device int32, never read back; slice_width is
+    then the widest slice) or j * slice_width ..; it reads the x columns j * rank .. of the segment's own rank."""
+    (S, XW), (num_lora, N_out, R) = x.shape, weights.shape
+    assert XW == num_slices * R and x.dtype == weights.dtype == out.dtype and lora_ranks.numel() >= num_lora
+    assert x.stride(1) == 1 and out.stride(1) == 1 and weights.is_contiguous()
+    assert out.shape == (S, N_out)
+    assert scalings.dtype == torch.float32 and scalings.is_contiguous() and scalings.numel() >= num_lora
+    if n_offs is not None:
+        assert n_offs.dtype == torch.int32 and n_offs.is_contiguous() and n_offs.numel() == num_slices + 1
+        assert slice_width is not None, "with device offsets the host gives the widest slice"
+    elif slice_width is None:
+        slice_width = N_out // num_slices
+    check(lib.mi_lora_expand(_ptr(x), _ptr(weights), _ptr(out), *_lora_batch_args(seg_indptr, weight_indices, lora_ranks, bs),
+                             _ptr(scalings), _ptr(n_offs), slice_width, num_slices, S, N_out, R, num_lora, x.stride(0),
+                             out.stride(0), bs, max_len, _dt(x), _stream()), "mi_lora_expand")
+    return out
+
+
 # -------------------------------------------------------------------------- int4
 def w4_repack(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, group_size: int,
               layout: int, g_idx: Optional[torch.Tensor] = None):

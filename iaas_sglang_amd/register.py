@@ -13,6 +13,9 @@ registration wraps those seams without editing any reference file (SURVEY sectio
        scheduler takes its one-launch branch instead of the per-request python loop, schedule_batch.py:1290-1309)
   4. QUANTIZATION_METHODS["fp8"|"awq"|"gptq"|"w8a8_int8"] -> our configs; awq/gptq are moved out of the
      vllm-gated table (quantization/__init__.py:75-120)
+  5. get_backend_from_name (lora/backend/base_backend.py:120-133) -> MiLoRABackend for --lora-backend mi355x, in the
+     defining module and in lora_manager, which imported the function by name (lora_manager.py:25); the option has no
+     argparse choices (server_args.py:1117-1121)
 
 Usage (in the process that launches the server, before arguments are parsed):
     import iaas_sglang_amd.register as r; r.register()
@@ -72,6 +75,9 @@ def register(override_quantization: bool = True) -> bool:
             q.QUANTIZATION_METHODS[name] = cfg
             q.BASE_QUANTIZATION_METHODS[name] = cfg
             q.VLLM_QUANTIZATION_METHODS.pop(name, None)
+
+    # 5. LoRA backend lookup
+    install_lora_backend()
     _registered = True
     return True
 
@@ -117,4 +123,28 @@ def install_scheduler_helpers(schedule_batch=None, forward_batch_info=None) -> b
     schedule_batch.write_req_to_token_pool_triton = _GridLaunch(write_req_to_token_pool)
     schedule_batch.get_last_loc_triton = get_last_loc
     forward_batch_info.compute_position_triton = compute_position
+    return True
+
+
+def install_lora_backend(base_backend=None, lora_manager=None) -> bool:
+    """Make `get_backend_from_name("mi355x")` return MiLoRABackend, in the module that defines the function and in
+    lora_manager, which holds its own reference to it (modules given, or imported from an installed SGLang).  Every
+    other name goes to the original function."""
+    try:
+        if base_backend is None:
+            import sglang.srt.lora.backend.base_backend as base_backend
+        if lora_manager is None:
+            import sglang.srt.lora.lora_manager as lora_manager
+    except Exception:
+        return False
+    orig = base_backend.get_backend_from_name
+
+    def get_backend_from_name(name: str):
+        if name == BACKEND_NAME:
+            from .lora_backend import MiLoRABackend
+            return MiLoRABackend
+        return orig(name)
+
+    base_backend.get_backend_from_name = get_backend_from_name
+    lora_manager.get_backend_from_name = get_backend_from_name
     return True

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 13
+#define MI_ABI_VERSION 14
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -378,6 +378,50 @@ int64_t mi_bf16_gemm_tile_workspace_bytes(int64_t M, int64_t N, int64_t K);
  * same arguments are accepted there (mi_bf16_gemm_tile itself starts with this call). */
 int mi_bf16_gemm_tile_check(const void* x, const void* w_nk, const void* out, int64_t M, int64_t N, int64_t K,
                             int64_t lda, int64_t ldb, int64_t ldo, int dtype, int out_dtype);
+
+/* ------------------------------------------------ multi-LoRA segmented GEMMs */
+
+/* A batch is `bs` segments of consecutive rows: p = seg_indptr (int32 [bs+1]), segment b owns rows p[b] .. p[b+1] and
+ * uses adapter a = weight_indices[b] (int32 [bs]) at rank rho = lora_ranks[a] ([num_lora]; int64 when ranks_is_i64, the
+ * reference's eager path, else int32, its graph path).  Of the batch only `bs` and `max_len` (an upper bound of the
+ * segment lengths; rows past it are not computed, as in the reference) are host values: everything else is read from
+ * device memory by the kernels, so a captured launch follows batch info rewritten in place (lora_manager.py:74-100,
+ * 248-256).  Segment lengths come from seg_indptr (the reference's seg_lens is a float tensor on its eager decode
+ * path, lora_manager.py:271-275).  A segment outside [0, S], an adapter outside [0, num_lora) or a rank <= 0 is skipped.
+ *
+ * Shrink.  x [S,K] (row stride ldx), weights [num_lora, N, K] contiguous with N = stack_num * r_max (stack_num 1..3),
+ *   out [S,N] (row stride ldo), all `dtype`.  For n < n_b = min(N, stack_num * rho):
+ *     out[p[b]+i, n] = round_T(sum_k x[p[b]+i, k] * W[a, n, k])     (fp32 accumulation, one rounding)
+ *   Columns >= n_b of that segment's rows are NOT written; rho = 0 writes nothing.  max_len <= 16 runs the decode
+ *   kernel (4 waves split K, summed in wave order), longer batches 64-row blocks that hold the whole width.
+ *   MI_ERR_UNSUPPORTED, before any launch, unless K % 8 == 0, r_max % 8 == 0, r_max <= 256, N <= 1024, ldx % 8 == 0,
+ *   ldo % 8 == 0, x / weights / out 16-byte aligned and N*K*2 < 2^32, 64*ldx*2 < 2^32, 64*ldo*2 < 2^32 (32-bit lane
+ *   offsets inside an adapter's matrix and a row block).
+ * replaces: sgemm_lora_a_fwd, lora/triton_ops/sgemm_lora_a.py:8-170. */
+int mi_lora_shrink(const void* x, const void* weights, void* out, const int32_t* seg_indptr,
+                   const int32_t* weight_indices, const void* lora_ranks, int ranks_is_i64, int64_t S, int64_t N,
+                   int64_t K, int64_t stack_num, int64_t num_lora, int64_t ldx, int64_t ldo, int64_t bs,
+                   int64_t max_len, int dtype /* MI_BF16 | MI_FP16 */, void* stream);
+
+/* Expand.  x [S, num_slices*R] is the shrink output (row stride ldx), weights [num_lora, N_out, R] contiguous with
+ *   R = r_max, out [S, N_out] (row stride ldo) is updated IN PLACE; scalings fp32 [num_lora].  Slice j < num_slices <= 3
+ *   covers output columns o_j .. o_{j+1}: o = n_offs, a DEVICE int32 [num_slices+1] (the reference's output_offset,
+ *   never read back; slice_width is then the host's bound of the slice widths, the reference's max_qkv_out_dim), or,
+ *   with n_offs null, o_j = j * slice_width.  With rho' = min(R, rho) slice j reads x columns j*rho' .. j*rho'+rho'
+ *   (the offset uses the ADAPTER's rank, qkv_lora_b.py:77,91):
+ *     acc = sum_{k<rho'} x[p[b]+i, j*rho'+k] * W[a, o_j+n, k]       (fp32; nothing at k >= rho' enters the sum)
+ *     out[p[b]+i, o_j+n] = round_T(float(round_T(acc * scalings[a])) + float(out_before))
+ *   (two roundings, the reference's, qkv_lora_b.py:117-124).  rho = 0 leaves the segment's rows untouched.  Ranks
+ *   that are multiples of 8 load 16-byte vectors, others element by element.
+ *   MI_ERR_UNSUPPORTED, before any launch, unless R % 8 == 0, R <= 256, ldx % 8 == 0, ldo % 8 == 0, x / weights / out
+ *   16-byte aligned and N_out*R*2 < 2^32, 16*ldx*2 < 2^32, 16*ldo*2 < 2^32 (32-bit lane offsets).
+ * replaces: sgemm_lora_b_fwd (lora/triton_ops/sgemm_lora_b.py), qkv_lora_b_fwd (qkv_lora_b.py:8-198) and
+ * gate_up_lora_b_fwd (gate_up_lora_b.py). */
+int mi_lora_expand(const void* x, const void* weights, void* out, const int32_t* seg_indptr,
+                   const int32_t* weight_indices, const void* lora_ranks, int ranks_is_i64, const float* scalings,
+                   const int32_t* n_offs /* nullable, device */, int64_t slice_width, int64_t num_slices, int64_t S,
+                   int64_t N_out, int64_t R, int64_t num_lora, int64_t ldx, int64_t ldo, int64_t bs, int64_t max_len,
+                   int dtype /* MI_BF16 | MI_FP16 */, void* stream);
 
 /* ------------------------------------------------------------------ INT8 W8A8 */
 
