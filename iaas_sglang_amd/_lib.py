@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_hotpath.so")
 
-ABI_VERSION = 14        # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
+ABI_VERSION = 15        # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
 MI_BF16, MI_FP16, MI_F32 = 0, 1, 2
 MI_SCALE_TENSOR, MI_SCALE_ROW = 0, 1
 MI_W4_AWQ, MI_W4_GPTQ = 0, 1
@@ -43,6 +43,7 @@ SIGNATURES = {
                                      _f, _f, _i64, _i64, _p, _i64, _p, _int, _p]),
     "mi_decode_attn_fp8kv": (_int, [_p, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64,
                                     _i64, _i64, _f, _f, _i64, _i64, _p, _i64, _p, _int, _p]),
+    "mi_mla_attn": (_int, [_p] * 7 + [_i64] * 8 + [_f, _i64, _i64, _p, _i64, _p, _int, _p]),
     "mi_extend_attn": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                               _i64, _i64, _i64, _i64, _f, _f, _int, _i64, _int, _p]),
     "mi_extend_attn_paged": (_int, [_p] * 11 + [_i64] * 12 + [_f, _f, _int, _i64, _int, _p]),

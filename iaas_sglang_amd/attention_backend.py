@@ -83,7 +83,10 @@ class MiAttnBackend(AttentionBackend):
         self.num_head = mc.num_attention_heads // tp
         self.num_kv_head = mc.get_num_kv_heads(tp) if hasattr(mc, "get_num_kv_heads") else mc.num_key_value_heads
         self.max_context_len = mc.context_len
-        self.v_head_dim = model_runner.token_to_kv_pool.get_value_buffer(0).shape[-1]
+        vb = model_runner.token_to_kv_pool.get_value_buffer(0)
+        self.v_head_dim = vb.shape[-1]
+        # latent (MLA) pool: one [slots, 1, 576] buffer per layer, the value is the view of its first 512 elements
+        self.mla_pool = vb.dim() == 3 and tuple(vb.shape[1:]) == (1, 512) and vb.stride(0) == 576
         sa = getattr(model_runner, "server_args", None)
         # --triton-attention-num-kv-splits (server_args.py:210) is reused as the split cap
         self.max_kv_splits = int(os.environ.get("MI_ATTN_MAX_KV_SPLITS",
@@ -338,6 +341,22 @@ class MiAttnBackend(AttentionBackend):
             ext_cpu = forward_batch.extend_seq_lens_cpu
             prefix_sum = int(sum(prefix_cpu)) if prefix_cpu is not None else int(forward_batch.extend_prefix_lens.sum())
             max_ext = int(max(ext_cpu)) if ext_cpu is not None else int(forward_batch.extend_seq_lens.max())
+            if self.mla_pool:
+                # MLA attends the new tokens from the pool as well: indices over the WHOLE sequences (req_to_token holds
+                # the new slots already), row t of a request then sees the keys up to its own (mi_mla_attn)
+                kv_indptr = ops.kv_indptr(forward_batch.seq_lens, self.kv_indptr)
+                kv_indices = torch.empty(max(int(forward_batch.seq_lens_sum), 1), dtype=torch.int32, device=self.device)
+                ops.kv_indices(self.req_to_token, forward_batch.req_pool_indices, forward_batch.seq_lens, kv_indptr,
+                               kv_indices)
+                qo_indptr = ops.kv_indptr(forward_batch.extend_seq_lens, self.qo_indptr)
+                tokens = int(sum(ext_cpu)) if ext_cpu is not None else int(forward_batch.extend_seq_lens.sum())
+                # one workgroup per (token, 16 heads): split the keys only when that leaves most of the chip idle
+                wgs = max(tokens * -(-self.num_head // 16), 1)
+                keys = int(forward_batch.seq_lens_sum) // max(bs, 1)
+                splits = max(1, min(32, 1024 // wgs, keys // 512)) if wgs < 768 else 1
+                self.forward_metadata = ForwardMetadata(kv_indptr, kv_indices, qo_indptr, max_ext, splits,
+                                                        self._workspace(tokens, splits))
+                return
             kv_indptr = ops.kv_indptr(forward_batch.extend_prefix_lens, self.kv_indptr)
             kv_indices = torch.empty(max(prefix_sum, 1), dtype=torch.int32, device=self.device)
             ops.kv_indices(self.req_to_token, forward_batch.req_pool_indices, forward_batch.extend_prefix_lens,
@@ -587,13 +606,56 @@ class MiAttnBackend(AttentionBackend):
             raise NotImplementedError(f"MiAttnBackend: KV pool dtype {k_buf.dtype} with {k.dtype} activations")
         ops.kv_write(k_buf, v_buf, forward_batch.out_cache_loc, k, v)
 
+    @staticmethod
+    def _is_mla_buffer(k_buf) -> bool:
+        return k_buf.dim() == 3 and k_buf.shape[1] == 1 and k_buf.shape[2] == 576
+
+    def _forward_mla(self, q, k, layer, forward_batch, save_kv_cache, fp8_out_scale, extend: bool):
+        """qk_head_dim != v_head_dim: absorbed MLA over the latent pool (triton_backend.py:642-643, 701-702 run the same
+        MQA form through their general kernels).  `k` is the new tokens' whole latent row [tokens, 1, 576]; it is
+        written to the pool first and attended from there, decode and extend alike (mi_mla_attn).  Returns
+        [tokens, Hq * 512]."""
+        kv_buf = forward_batch.token_to_kv_pool.get_key_buffer(layer.layer_id)
+        if not (layer.qk_head_dim == 576 and layer.v_head_dim == 512 and self._is_mla_buffer(kv_buf)):
+            raise NotImplementedError(f"MiAttnBackend: MLA geometry {layer.qk_head_dim} -> {layer.v_head_dim} over a pool "
+                                      f"of rows {tuple(kv_buf.shape[1:])} has no kernel (576 -> 512 over [slots, 1, 576])")
+        if kv_buf.element_size() == 1:
+            raise NotImplementedError("MiAttnBackend: MLA over an fp8 latent pool has no kernel (bf16 / fp16)")
+        lw = getattr(layer, "sliding_window_size", None)
+        if lw is not None and lw > -1:
+            raise NotImplementedError("MiAttnBackend: MLA with a sliding window has no kernel")
+        if getattr(layer, "logit_cap", 0.0) or 0.0:
+            raise NotImplementedError("MiAttnBackend: MLA with logit_cap has no kernel")
+        if fp8_out_scale is not None:
+            raise NotImplementedError("MiAttnBackend: MLA with a fused fp8 output (fp8_out_scale) has no kernel")
+        mode = forward_batch.forward_mode
+        md = self.forward_metadata
+        if mode.is_target_verify() or mode.is_draft_extend() or md.custom_mask is not None or \
+                getattr(forward_batch, "spec_info", None) is not None:
+            raise NotImplementedError("MiAttnBackend: MLA in the speculative modes (TARGET_VERIFY, DRAFT_EXTEND) has no kernel")
+        if extend and not save_kv_cache:
+            raise NotImplementedError("MiAttnBackend: MLA extend attends the new tokens from the pool (save_kv_cache=False)")
+        if q.dtype != kv_buf.dtype or (save_kv_cache and k.dtype != kv_buf.dtype):
+            raise NotImplementedError(f"MiAttnBackend: MLA pool dtype {kv_buf.dtype} with {q.dtype} activations")
+        if save_kv_cache:
+            k2 = k.reshape(-1, 576)
+            ops.mla_kv_write(kv_buf, forward_batch.out_cache_loc, k2[:, :512], k2[:, 512:])
+        H = layer.tp_q_head_num
+        q3 = q.reshape(-1, H, 576)
+        o = q.new_empty((q3.shape[0], H * 512))
+        # token-granular indices whatever page_size is: the latent kernel reads no page tables
+        ops.mla_attention(q3, kv_buf, o.view(-1, H, 512), md.kv_indptr, md.kv_indices, layer.scaling,
+                          md.qo_indptr if extend else None, md.num_kv_splits, md.workspace,
+                          split_chunk=md.split_chunk, work=md.work)
+        return o
+
     def forward_decode(self, q, k, v, layer, forward_batch, save_kv_cache=True, fp8_out_scale=None):
         """`fp8_out_scale` (extension, passed through AttentionBackend.forward's **kwargs): the static input
         scale of the following FP8 linear; the output is then returned already quantised (fp8), bit-identical
         to quantising the bf16 result -- the merge stage writes it directly."""
         q = q.reshape(-1, layer.tp_q_head_num * layer.qk_head_dim)
         if layer.qk_head_dim != layer.v_head_dim:
-            raise NotImplementedError("MiAttnBackend: qk_head_dim != v_head_dim (MLA) is out of scope")
+            return self._forward_mla(q, k, layer, forward_batch, save_kv_cache, fp8_out_scale, extend=False)
         if save_kv_cache:
             self._save_kv(forward_batch, layer, k, v)
         k_buf, v_buf = self._pool_buffers(forward_batch, layer)
@@ -663,7 +725,9 @@ class MiAttnBackend(AttentionBackend):
         fp8-pool forms quantise their T-typed output in a second launch.  `q_rope` = (positions, cos_sin_cache_t): q
         is unrotated and the kernel applies NeoX RoPE as it loads Q -- only where extend_rotates_q() said so."""
         if layer.qk_head_dim != layer.v_head_dim:
-            raise NotImplementedError("MiAttnBackend: qk_head_dim != v_head_dim (MLA) is out of scope")
+            if q_rope is not None:
+                raise NotImplementedError("MiAttnBackend: MLA attention does not rotate Q (q_rope)")
+            return self._forward_mla(q, k, layer, forward_batch, save_kv_cache, fp8_out_scale, extend=True)
         if save_kv_cache:
             self._save_kv(forward_batch, layer, k, v)
         k_buf, v_buf = self._pool_buffers(forward_batch, layer)

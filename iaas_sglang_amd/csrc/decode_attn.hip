@@ -779,6 +779,21 @@ MI_INTERNAL int mi_attn_merge_splits(const float* ws_o, const float* ws_ml, void
   return MI_OK;
 }
 
+// mla_attn.hip: the D = 512 instance (MLA latent values), with the live-split rule of a work list / device plan
+MI_INTERNAL int mi_attn_merge_splits512(const float* ws_o, const float* ws_ml, void* o, int64_t rows, int64_t num_q_heads,
+                                        int64_t num_splits, int64_t stride_o_tok, const int32_t* kv_indptr,
+                                        int64_t split_chunk, const int32_t* plan, int dtype, void* stream) {
+  const int64_t n_bh = rows * num_q_heads;
+  const unsigned blocks = (unsigned)cdiv64(n_bh, 4);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MI_BF16)
+    decode_merge_kernel<bf16_t, 512><<<blocks, 256, 0, st>>>(ws_o, ws_ml, (bf16_t*)o, n_bh, (int)num_q_heads, (int)num_splits, stride_o_tok, nullptr, nullptr, 1.f, kv_indptr, (int32_t)split_chunk, plan);
+  else
+    decode_merge_kernel<f16_t, 512><<<blocks, 256, 0, st>>>(ws_o, ws_ml, (f16_t*)o, n_bh, (int)num_q_heads, (int)num_splits, stride_o_tok, nullptr, nullptr, 1.f, kv_indptr, (int32_t)split_chunk, plan);
+  MI_CHECK_LAUNCH();
+  return MI_OK;
+}
+
 extern "C" int64_t mi_decode_attn_workspace_bytes(int64_t batch, int64_t num_q_heads,
                                                   int64_t v_head_dim, int64_t num_splits) {
   if (num_splits <= 1) return 0;

@@ -116,6 +116,53 @@ class MHATokenToKVPool:
             ops.kv_write(kb, vb, loc, cache_k, cache_v)
 
 
+class MLATokenToKVPool:
+    """memory_pool.py:735-860 -- one latent buffer per layer, kv_buffer [size + page_size, 1, kv_lora_rank +
+    qk_rope_head_dim]: the whole row is the key, its first kv_lora_rank elements the value (a view).  bf16 / fp16 only:
+    the MLA attention kernel reads no fp8 rows."""
+
+    def __init__(self, size: int, page_size: int, dtype: torch.dtype, kv_lora_rank: int, qk_rope_head_dim: int,
+                 layer_num: int, device: str, enable_memory_saver: bool = False, start_layer: Optional[int] = None,
+                 end_layer: Optional[int] = None):
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"MLATokenToKVPool: KV dtype {dtype} has no kernel (bf16 / fp16)")
+        self.size, self.page_size, self.dtype, self.device = size, page_size, dtype, device
+        self.store_dtype = dtype
+        self.layer_num = layer_num
+        self.start_layer = start_layer or 0
+        self.end_layer = end_layer or layer_num - 1
+        self.kv_lora_rank, self.qk_rope_head_dim = kv_lora_rank, qk_rope_head_dim
+        # slot 0 (the first page) is the sink padded tokens write to
+        self.kv_buffer = [torch.zeros((size + page_size, 1, kv_lora_rank + qk_rope_head_dim), dtype=dtype, device=device)
+                          for _ in range(layer_num)]
+        self.token_stride = kv_lora_rank + qk_rope_head_dim
+        self.layer_transfer_counter = None
+        self.mem_usage = self.get_kv_size_bytes() / (1 << 30)
+
+    def get_kv_size_bytes(self):
+        return sum(b.numel() * b.element_size() for b in self.kv_buffer)
+
+    def get_key_buffer(self, layer_id: int) -> torch.Tensor:
+        return self.kv_buffer[layer_id - self.start_layer]
+
+    def get_value_buffer(self, layer_id: int) -> torch.Tensor:
+        return self.kv_buffer[layer_id - self.start_layer][..., : self.kv_lora_rank]
+
+    def get_kv_buffer(self, layer_id: int):
+        return self.get_key_buffer(layer_id), self.get_value_buffer(layer_id)
+
+    def set_kv_buffer(self, layer, loc: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor = None):
+        """kv_buffer[layer][loc] = cache_k (the whole latent row; cache_v is ignored, memory_pool.py:839-852)."""
+        cache_k = cache_k.reshape(loc.shape[0], -1)
+        self.set_mla_kv_buffer(layer, loc, cache_k[:, : self.kv_lora_rank], cache_k[:, self.kv_lora_rank:])
+
+    def set_mla_kv_buffer(self, layer, loc: torch.Tensor, cache_k_nope: torch.Tensor, cache_k_rope: torch.Tensor):
+        """kv_buffer[layer][loc] = cat(cache_k_nope, cache_k_rope) in one scatter launch (memory_pool.py:859-882)."""
+        if cache_k_nope.dtype != self.dtype:
+            cache_k_nope, cache_k_rope = cache_k_nope.to(self.dtype), cache_k_rope.to(self.dtype)
+        ops.mla_kv_write(self.kv_buffer[layer.layer_id - self.start_layer], loc, cache_k_nope, cache_k_rope)
+
+
 class TokenToKVPoolAllocator:
     """allocator.py:113-153 (page_size = 1): a free list of int64 slot indices, served from the front."""
 

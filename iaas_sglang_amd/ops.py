@@ -260,6 +260,51 @@ def decode_attention_paged(q: torch.Tensor, k_buf: torch.Tensor, v_buf: torch.Te
     return o if o is not None else o_fp8
 
 
+def mla_kv_write(kv_cache: torch.Tensor, loc: torch.Tensor, k_nope: torch.Tensor, k_rope: torch.Tensor) -> None:
+    """kv_cache[loc, 0, :R] = k_nope ; kv_cache[loc, 0, R:] = k_rope  (MLATokenToKVPool.set_mla_kv_buffer): the scatter
+    kernel of kv_write with the "value" cache pointed R elements into the same rows."""
+    assert loc.dtype == torch.int64 and loc.is_contiguous()
+    T = loc.shape[0]
+    k_nope, k_rope = k_nope.reshape(T, -1), k_rope.reshape(T, -1)
+    R, P = k_nope.shape[1], k_rope.shape[1]
+    assert kv_cache.dim() == 3 and kv_cache.shape[1] == 1 and kv_cache.shape[2] == R + P and kv_cache.stride(2) == 1
+    assert k_nope.dtype == kv_cache.dtype and k_rope.dtype == kv_cache.dtype
+    assert k_nope.stride(1) == 1 and k_rope.stride(1) == 1
+    check(lib.mi_kv_write(_ptr(kv_cache), _ptr(kv_cache[:, :, R:]), _ptr(loc), _ptr(k_nope), _ptr(k_rope), T, R, P,
+                          kv_cache.stride(0), kv_cache.stride(0), k_nope.stride(0), k_rope.stride(0), _dt(kv_cache),
+                          _stream()), "mi_kv_write")
+
+
+def mla_attention(q: torch.Tensor, kv_buf: torch.Tensor, o: torch.Tensor, kv_indptr_t: torch.Tensor,
+                  kv_indices_t: torch.Tensor, sm_scale: float, qo_indptr: Optional[torch.Tensor] = None,
+                  num_splits: int = 1, workspace: Optional[torch.Tensor] = None, split_chunk: int = 0,
+                  work=None) -> torch.Tensor:
+    """MLA attention over a latent pool: q [T,H,576], kv_buf [slots,1,576], o [T,H,512].  Decode (qo_indptr None, one
+    row per request) or plain extend (qo_indptr int32 [B+1]; the new tokens are in the pool already and row t sees the
+    keys up to its own).  Splits, workspace, split_chunk and work / plan (decode only) as in decode_attention."""
+    T, H, Dq = q.shape
+    Dv = o.shape[2]
+    assert kv_buf.dim() == 3 and kv_buf.shape[1] == 1 and kv_buf.shape[2] == Dq and kv_buf.stride(2) == 1
+    assert q.stride(2) == 1 and q.stride(1) == Dq and o.stride(2) == 1 and o.stride(1) == Dv and o.shape[:2] == q.shape[:2]
+    assert kv_buf.dtype == q.dtype and o.dtype == q.dtype
+    assert kv_indptr_t.dtype == torch.int32 and kv_indices_t.dtype == torch.int32
+    B = kv_indptr_t.shape[0] - 1
+    if qo_indptr is not None:
+        assert qo_indptr.dtype == torch.int32 and qo_indptr.shape[0] == B + 1
+    else:
+        assert B == T
+    if num_splits > 1:
+        need = decode_workspace_numel(T, H, Dv, num_splits)
+        assert workspace is not None and workspace.dtype == torch.float32 and workspace.numel() >= need
+    # fp32 goes down as MI_F32: the library refuses it (MI_ERR_UNSUPPORTED), like any other geometry it has no kernel for
+    dt = MI_F32 if q.dtype == torch.float32 else _dt(q)
+    check(lib.mi_mla_attn(_ptr(q), _ptr(kv_buf), _ptr(o), _ptr(qo_indptr), _ptr(kv_indptr_t), _ptr(kv_indices_t),
+                          _ptr(workspace) if num_splits > 1 else None, B, T, H, Dq, Dv, q.stride(0), o.stride(0),
+                          kv_buf.stride(0), float(sm_scale), int(num_splits), int(split_chunk), *_work_args(work),
+                          dt, _stream()), "mi_mla_attn")
+    return o
+
+
 def extend_attention(q: torch.Tensor, k_ext: torch.Tensor, v_ext: torch.Tensor, o: torch.Tensor,
                      k_buf: torch.Tensor, v_buf: torch.Tensor, qo_indptr: torch.Tensor,
                      kv_indptr_t: torch.Tensor, kv_indices_t: torch.Tensor, max_extend_len: int,

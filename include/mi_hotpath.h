@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 14
+#define MI_ABI_VERSION 15
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -190,6 +190,29 @@ int mi_decode_attn_fp8kv(const void* q, const void* k_buf, const void* v_buf, vo
                          int64_t stride_v_slot, float sm_scale, float logit_cap, int64_t num_splits,
                          int64_t split_chunk, const int32_t* work, int64_t num_work, const int32_t* plan, int dtype,
                          void* stream);
+
+/* MLA (multi-head latent attention, absorbed form) over a latent KV pool, decode and plain extend in one kernel.
+ *   q [T,Hq,576] (stride_q_tok elements between tokens, heads 576 apart); kv_buf [slots,1,576] (stride_kv_slot elements
+ *   between slots, 0 < stride < 2^31): kv_lora_rank 512 + qk_rope_head_dim 64, one row is the key of every q head and
+ *   -- its first 512 elements -- the value; o [T,Hq,512] (heads 512 apart).
+ *   o[t,h] = softmax_{j < n_t}(sm_scale * q[t,h] . kv_buf[idx_j, 0, :576]) . kv_buf[idx_j, 0, :512],
+ *   idx = kv_indices[kv_indptr[b] ..] of the request b that owns row t.  Keys come from the pool only: the caller writes
+ *   the new tokens first (mi_kv_write).
+ *   decode (qo_indptr == NULL, total_tokens == batch): b = t, n_t = S_b = kv_indptr[b+1] - kv_indptr[b].
+ *   extend (qo_indptr int32 [batch+1]): b owns rows qo_indptr[b] .. qo_indptr[b+1]-1 (found in the kernel) and
+ *   n_t = S_b - (qo_indptr[b+1] - 1 - t): the last new token sees all S_b keys, each earlier one a key fewer.
+ *   qk_head_dim / v_head_dim other than 576 / 512, or a dtype other than bf16 / fp16: MI_ERR_UNSUPPORTED.
+ *   num_splits / split_chunk / workspace as in mi_decode_attn (the split rule applied to n_t; workspace of
+ *   mi_decode_attn_workspace_bytes(total_tokens, Hq, 512, num_splits)); work / plan as in mi_decode_attn, decode only.
+ *   No sliding window, logit cap or custom mask.
+ * replaces: decode_attention_fwd / extend_attention_fwd as TritonAttnBackend calls them for MLA models over
+ * MLATokenToKVPool (triton_backend.py:115,642-643,701-702; memory_pool.py:735-860). */
+int mi_mla_attn(const void* q, const void* kv_buf, void* o, const int32_t* qo_indptr /* nullable */,
+                const int32_t* kv_indptr, const int32_t* kv_indices, void* workspace, int64_t batch,
+                int64_t total_tokens, int64_t num_q_heads, int64_t qk_head_dim, int64_t v_head_dim,
+                int64_t stride_q_tok, int64_t stride_o_tok, int64_t stride_kv_slot, float sm_scale,
+                int64_t num_splits, int64_t split_chunk, const int32_t* work, int64_t num_work, const int32_t* plan,
+                int dtype, void* stream);
 
 /* Ragged extend (prefill-with-prefix) attention.
  *   q_ext [E,Hq,D], k_ext/v_ext [E,Hkv,D] : the new tokens, request i owns rows
