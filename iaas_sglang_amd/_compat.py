@@ -396,3 +396,49 @@ except Exception:
 
         def set_batch_info(self, batch_info: LoRABatchInfo):
             self.batch_info = batch_info
+
+try:  # pragma: no cover - exercised only inside an SGLang install
+    from sglang.srt.layers.moe.fused_moe_triton.layer import FusedMoEMethodBase, UnquantizedFusedMoEMethod
+except Exception:
+
+    class FusedMoEMethodBase(QuantizeMethodBase):
+        """python/sglang/srt/layers/moe/fused_moe_triton/layer.py:69-93."""
+
+        @abstractmethod
+        def create_weights(self, layer: torch.nn.Module, num_experts: int, hidden_size: int, intermediate_size: int,
+                           params_dtype: torch.dtype, **extra_weight_attrs):
+            raise NotImplementedError
+
+        @abstractmethod
+        def apply(self, layer: torch.nn.Module, x: torch.Tensor, router_logits: torch.Tensor, top_k: int,
+                  renormalize: bool, use_grouped_topk: bool) -> torch.Tensor:
+            raise NotImplementedError
+
+    class UnquantizedFusedMoEMethod(FusedMoEMethodBase):
+        """layer.py:96-277: the two expert parameters, w13_weight [E, 2I, H] (gate rows, then up rows) and w2_weight
+        [E, H, I]; the extra attributes (the layer's weight_loader) are set on both.  `apply` has no stand-in
+        arithmetic: the plugin class overrides it."""
+
+        def __init__(self, use_triton_kernels: bool = False):
+            super().__init__()
+            self.use_triton_kernels = use_triton_kernels
+
+        def create_weights(self, layer: torch.nn.Module, num_experts: int, hidden_size: int, intermediate_size: int,
+                           params_dtype: torch.dtype, **extra_weight_attrs):
+            for name, shape in (("w13_weight", (num_experts, 2 * intermediate_size, hidden_size)),
+                                ("w2_weight", (num_experts, hidden_size, intermediate_size))):
+                w = Parameter(torch.empty(*shape, dtype=params_dtype), requires_grad=False)
+                layer.register_parameter(name, w)
+                for key, value in extra_weight_attrs.items():
+                    setattr(w, key, value)
+
+        def process_weights_after_loading(self, layer: torch.nn.Module) -> None:
+            return
+
+        def apply(self, layer: torch.nn.Module, x: torch.Tensor, router_logits: torch.Tensor, top_k: int,
+                  renormalize: bool, use_grouped_topk: bool, topk_group: Optional[int] = None,
+                  num_expert_group: Optional[int] = None, num_fused_shared_experts: int = 0,
+                  custom_routing_function=None, correction_bias: Optional[torch.Tensor] = None,
+                  activation: str = "silu", apply_router_weight_on_input: bool = False, inplace: bool = True,
+                  no_combine: bool = False, routed_scaling_factor: Optional[float] = None) -> torch.Tensor:
+            raise NotImplementedError

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_hotpath.so")
 
-ABI_VERSION = 15        # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
+ABI_VERSION = 16       # MI_ABI_VERSION of include/mi_hotpath.h this table was written against
 MI_BF16, MI_FP16, MI_F32 = 0, 1, 2
 MI_SCALE_TENSOR, MI_SCALE_ROW = 0, 1
 MI_W4_AWQ, MI_W4_GPTQ = 0, 1
@@ -76,6 +76,9 @@ SIGNATURES = {
     "mi_bf16_gemm_tile_check": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int]),
     "mi_lora_shrink": (_int, [_p] * 6 + [_int] + [_i64] * 9 + [_int, _p]),
     "mi_lora_expand": (_int, [_p] * 6 + [_int, _p, _p] + [_i64] * 10 + [_int, _p]),
+    "mi_moe_topk_softmax": (_int, [_p, _p, _p, _i64, _i64, _i64, _i64, _int, _int, _p]),
+    "mi_moe_workspace_bytes": (_i64, [_i64] * 5),
+    "mi_moe_fused_experts": (_int, [_p] * 7 + [_i64] * 8 + [_f, _int, _int, _p]),
     "mi_w4_repack": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _int, _int, _p]),
     "mi_w4a16_gemm": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _int, _p, _i64, _p]),
     "mi_w4a16_gemm_workspace_bytes": (_i64, [_i64, _i64, _i64]),

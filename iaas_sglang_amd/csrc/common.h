@@ -121,6 +121,12 @@ static inline int mi_tune(const char* name, int dflt) {
 static inline constexpr int mi_tune(const char*, int dflt) { return dflt; }
 #endif
 
+// moe.hip: mi_moe_fused_experts (form 0) runs the tile form from T * k / E >= this many rows per expert on average,
+// the rows16 form below (MI_MOE_TILE_MIN_ROWS_PER_EXPERT).  profiles/moe_experts.txt: rows16 is faster at 1, 4 and 8
+// rows per expert, the tile form at 32, 128 and 512; nothing was timed between 8 and 32, 16 is where a second 16-row
+// block per expert begins
+constexpr int kMoeTileMinRowsPerExpert = 16;
+
 // LDS-DMA (global -> LDS, 16 B per lane, LDS destination = wave-uniform byte address + lane*16) issued
 // from inline asm so that hipcc does NOT know LDS is being written asynchronously: with the builtin it
 // puts an `s_waitcnt vmcnt(0)` in front of every later ds_read that might alias, which drains the whole

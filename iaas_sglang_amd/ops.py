@@ -843,6 +843,52 @@ def lora_expand(x: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, seg_i
     return out
 
 
+# -------------------------------------------------------------------- mixture of experts
+_MOE_FORMS = {"auto": 0, "rows16": 1, "tile": 2}
+_GATING_DT = {torch.float32: MI_F32, **_DT}
+
+
+def moe_topk_softmax(gating: torch.Tensor, k: int, renormalize: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """softmax over the E logits of each row of gating [T,E] (fp32 / bf16 / fp16), then the top k: (weights fp32 [T,k],
+    ids int32 [T,k]); the lowest expert index wins a tie; weights are divided by their sum when `renormalize`."""
+    T, E = gating.shape
+    assert gating.stride(1) == 1, "rows of gating are contiguous"
+    if gating.dtype not in _GATING_DT:
+        raise MiHotpathError(f"unsupported gating dtype {gating.dtype} (fp32 / bf16 / fp16)")
+    weights = torch.empty(T, k, dtype=torch.float32, device=gating.device)
+    ids = torch.empty(T, k, dtype=torch.int32, device=gating.device)
+    check(lib.mi_moe_topk_softmax(_ptr(gating), _ptr(weights), _ptr(ids), T, E, k, gating.stride(0), int(renormalize),
+                                  _GATING_DT[gating.dtype], _stream()), "mi_moe_topk_softmax")
+    return weights, ids
+
+
+def moe_fused_experts(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, topk_weights: torch.Tensor,
+                      topk_ids: torch.Tensor, inplace: bool = False, routed_scaling_factor: Optional[float] = None,
+                      form: str = "auto", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [T,H] = routed_scaling_factor * sum_j topk_weights[t,j] * down_e(silu(gate_e(x[t])) * up_e(x[t])) with
+    e = topk_ids[t,j]; w13 [E, 2I, H] (gate rows, then up rows), w2 [E, H, I].  Slots whose id is outside [0, E) add
+    nothing.  `inplace` writes the result over x; else into `out` (row-strided allowed) or a fresh tensor.  The workspace
+    is the per-device GEMM scratch."""
+    (T, H), (E, I2, H2), k = x.shape, w13.shape, topk_ids.shape[1]
+    I = I2 // 2
+    assert H == H2 and I2 == 2 * I and w2.shape == (E, H, I) and x.dtype == w13.dtype == w2.dtype
+    assert x.stride(1) == 1 and w13.is_contiguous() and w2.is_contiguous()
+    assert topk_ids.shape == topk_weights.shape == (T, k) and topk_ids.is_contiguous() and topk_weights.is_contiguous()
+    assert topk_ids.dtype == torch.int32 and topk_weights.dtype == torch.float32
+    if inplace:
+        out = x
+    elif out is None:
+        out = torch.empty(T, H, dtype=x.dtype, device=x.device)
+    assert out.shape == (T, H) and out.dtype == x.dtype and out.stride(1) == 1
+    ws_bytes = max(lib.mi_moe_workspace_bytes(T, E, k, H, I), 0)      # (< 0: the call below reports why)
+    ws = _gemm_workspace(max(ws_bytes, 16), x.device)
+    check(lib.mi_moe_fused_experts(_ptr(x), _ptr(w13), _ptr(w2), _ptr(topk_weights), _ptr(topk_ids), _ptr(out), _ptr(ws),
+                                   ws.numel(), T, E, k, H, I, x.stride(0), out.stride(0),
+                                   1.0 if routed_scaling_factor is None else float(routed_scaling_factor),
+                                   _MOE_FORMS[form], _dt(x), _stream()), "mi_moe_fused_experts")
+    return out
+
+
 # -------------------------------------------------------------------------- int4
 def w4_repack(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor, group_size: int,
               layout: int, g_idx: Optional[torch.Tensor] = None):

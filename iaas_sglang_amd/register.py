@@ -16,6 +16,9 @@ registration wraps those seams without editing any reference file (SURVEY sectio
   5. get_backend_from_name (lora/backend/base_backend.py:120-133) -> MiLoRABackend for --lora-backend mi355x, in the
      defining module and in lora_manager, which imported the function by name (lora_manager.py:25); the option has no
      argparse choices (server_args.py:1117-1121)
+  6. UnquantizedFusedMoEMethod in layers/moe/fused_moe_triton/layer.py -> MiUnquantizedFusedMoEMethod: FusedMoE.__init__
+     looks the name up in its own module when the layer has no quant_config (layer.py:513-516), so every unquantised
+     MoE layer built after register() runs the native router and expert kernels
 
 Usage (in the process that launches the server, before arguments are parsed):
     import iaas_sglang_amd.register as r; r.register()
@@ -78,6 +81,9 @@ def register(override_quantization: bool = True) -> bool:
 
     # 5. LoRA backend lookup
     install_lora_backend()
+
+    # 6. unquantised experts
+    install_fused_moe()
     _registered = True
     return True
 
@@ -147,4 +153,18 @@ def install_lora_backend(base_backend=None, lora_manager=None) -> bool:
 
     base_backend.get_backend_from_name = get_backend_from_name
     lora_manager.get_backend_from_name = get_backend_from_name
+    return True
+
+
+def install_fused_moe(layer_module=None) -> bool:
+    """Bind MiUnquantizedFusedMoEMethod over the name `UnquantizedFusedMoEMethod` in the module where FusedMoE.__init__
+    looks it up for a layer without a quant_config (module given, or imported from an installed SGLang).  The class
+    derives from the original, which it keeps for `create_weights` and the weight loaders."""
+    try:
+        if layer_module is None:
+            import sglang.srt.layers.moe.fused_moe_triton.layer as layer_module
+    except Exception:
+        return False
+    from .quantization.unquantized import MiUnquantizedFusedMoEMethod
+    layer_module.UnquantizedFusedMoEMethod = MiUnquantizedFusedMoEMethod
     return True

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 15
+#define MI_ABI_VERSION 16
 
 enum { MI_BF16 = 0, MI_FP16 = 1, MI_F32 = 2 };
 enum {
@@ -445,6 +445,42 @@ int mi_lora_expand(const void* x, const void* weights, void* out, const int32_t*
                    const int32_t* n_offs /* nullable, device */, int64_t slice_width, int64_t num_slices, int64_t S,
                    int64_t N_out, int64_t R, int64_t num_lora, int64_t ldx, int64_t ldo, int64_t bs, int64_t max_len,
                    int dtype /* MI_BF16 | MI_FP16 */, void* stream);
+
+/* ------------------------------------------------ mixture of experts (unquantised bf16 / fp16 experts) */
+
+/* Router.  gating [T,E] (row stride ldg elements; MI_F32, MI_BF16 or MI_FP16, converted to fp32 when loaded),
+ * topk_weights fp32 [T,k], topk_ids int32 [T,k], both contiguous.  p = softmax(gating[t]) in fp32; k rounds of arg-max,
+ * the LOWEST expert index winning a tie; weights are the p of the chosen experts, divided by their sum when
+ * `renormalize`.  MI_ERR_UNSUPPORTED unless E <= 256 and 1 <= k <= min(E, 8).
+ * replaces: fused_topk / topk_softmax, layers/moe/topk.py:95-121 (sgl-kernel csrc/moe/moe_topk_softmax_kernels.cu). */
+int mi_moe_topk_softmax(const void* gating, float* topk_weights, int32_t* topk_ids, int64_t T, int64_t E, int64_t k,
+                        int64_t ldg, int renormalize, int gating_dtype, void* stream);
+
+/* Bytes of the workspace of mi_moe_fused_experts (16-byte aligned): the sorted pair list, expert_indptr, the tile list
+ * and the [T*k, I] and [T*k, H] intermediates.  -1: the shape has no kernel. */
+int64_t mi_moe_workspace_bytes(int64_t T, int64_t E, int64_t k, int64_t H, int64_t I);
+
+/* Fused experts.  x [T,H] (row stride ldx), w13 [E, 2I, H] (gate rows, then up rows) and w2 [E, H, I] contiguous,
+ * topk_weights fp32 [T,k], topk_ids int32 [T,k], out [T,H] (row stride ldo; may alias x: every read of x is
+ * stream-ordered before the launch that writes out).  Four launches:
+ *   align    counting sort of the pairs p = t*k + j by expert e = topk_ids[p] into the workspace (sorted_ids,
+ *            expert_indptr [E+1], a list of row blocks); pairs with e outside [0, E) are dropped and add nothing.
+ *   gate_up  g = round_T(x[t] . w13[e, n]), u = round_T(x[t] . w13[e, I+n]), act[r, n] = round_T(silu(g) * u)
+ *            (fp32 accumulation; the SiLU arithmetic of mi_silu_and_mul; the [T*k, 2I] intermediate never exists)
+ *   down     y[p] = round_T((act[r] . w2[e]^T) * topk_weights[p])    (the weight meets the fp32 accumulator)
+ *   sum      out[t] = round_T(routed_scaling * sum_j float(y[t*k + j]))   (fp32, slot order)
+ * form: 0 chooses from T, k and E alone (a captured launch stays valid), 1 the rows16 form (row blocks of 16, weight
+ * fragments streamed through registers), 2 the tile form (128 x 128 blocks staged through LDS).
+ * MI_ERR_UNSUPPORTED, before any launch, unless H % 64 == 0, I % 16 == 0, E <= 256, k <= 8, dtype MI_BF16 / MI_FP16,
+ * ldx % 8 == 0, ldo % 8 == 0, all operands 16-byte aligned and 2*I*H*2 < 2^32 (32-bit lane offsets inside one expert's
+ * matrix; activation rows are addressed through 64-bit row pointers).  MI_ERR_INVALID when workspace_bytes is less
+ * than mi_moe_workspace_bytes().
+ * replaces: fused_experts, layers/moe/fused_moe_triton/fused_moe.py:1495-1728 (moe_align_block_size :711-791,
+ * fused_moe_kernel :314-525, silu_and_mul, moe_sum_reduce :1405-1487). */
+int mi_moe_fused_experts(const void* x, const void* w13, const void* w2, const float* topk_weights,
+                         const int32_t* topk_ids, void* out, void* workspace, int64_t workspace_bytes, int64_t T,
+                         int64_t E, int64_t k, int64_t H, int64_t I, int64_t ldx, int64_t ldo, float routed_scaling,
+                         int form /* 0 auto | 1 rows16 | 2 tile */, int dtype /* MI_BF16 | MI_FP16 */, void* stream);
 
 /* ------------------------------------------------------------------ INT8 W8A8 */
 
